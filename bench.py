@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- meshes/sec of the CAPE-affineconv_nz64 training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -13,6 +13,12 @@ adversarial step).  Inputs are resident in HBM before the timed region; weights 
 initialisers (random), data is synthetic N(0,1) displacements on the real SMPL mesh hierarchy.
 Prints ONE JSON line (rank 0).  Data-parallel (weak scaling): per-GPU batch fixed, one flat
 gradient all-reduce per step over RCCL.
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  ``--full`` adds the
+side measurements to it: per-kernel roofline, CPU baseline, exact-fp32 / bf16x6 comparison runs,
+the other BASELINE configs with the modelled scaling table, and for N > 1 the step with the
+exchange switched off.  ``--dump-outputs DIR`` writes what the last timed step computed
+(``dump_outputs``) before any of them runs.
 """
 import argparse
 import json
@@ -473,6 +479,29 @@ def extra_measurements(args, headline_ms, model):
     return extras, modelled_scaling(ms_by_batch, grad_bytes, late_fraction)
 
 
+DUMP_SAMPLE = 1 << 20     # entries kept of a larger flat buffer: at most 8 buffers x 4 MB, well under 64 MB in all
+
+
+def dump_outputs(runner, out_dir):
+    """What the timed step computed in its last replay, as ``out_dir/<name>.npy``: the loss values (float64) and, per
+    variable group, the updated variables, the gradient bucket and the optimiser state (float32).  A buffer longer than
+    DUMP_SAMPLE is reduced to a fixed sample: the same seeded, sorted index set for every buffer of that length."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    arrays = {k: v.detach().double().cpu().numpy() for k, v in runner.losses.items()}
+    for grp in runner._groups():
+        st = runner.model._opt_state[grp]
+        for name, key in (("variables", "flat"), ("gradients", "flat_grad"), ("optimizer_m", "m"), ("optimizer_v", "v")):
+            if key not in st:
+                continue
+            a = st[key].detach().float().cpu().numpy()
+            if a.size > DUMP_SAMPLE:
+                a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_SAMPLE, replace=False))]
+            arrays["%s_%s" % (name, grp)] = a
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def relaunch_under_torchrun(args):
     """`python bench.py --gpus N` with N > 1 and no torchrun environment: start the N ranks here (a harness valid
     for world_size 1..8 however it is invoked), one process per GPU, rendezvous on 127.0.0.1, and hand their output through.
@@ -510,6 +539,12 @@ def main():
                          "bf16 activations / bf16 operands with fp32 accumulation and fp32 master weights)")
     ap.add_argument('--gan', action='store_true', help='include the discriminator passes/update (adversarial step)')
     ap.add_argument('--no-graph', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the side measurements (per-kernel roofline, CPU baseline, exact-fp32 / '
+                         'bf16x6 comparison runs, extra configs + modelled scaling, exchange-off step for N > 1); the --no-* '
+                         'options below leave out single ones of them')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (losses, variables, gradients, optimiser state) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-extras', action='store_true',
@@ -521,6 +556,8 @@ def main():
                     help='hand every step a fresh batch of HOST numpy arrays (as fit() does): the PCIe-inclusive rate '
                          'quoted in DESIGN.md; never the headline value')
     args = ap.parse_args()
+    if not args.full:                  # a plain run measures the headline only
+        args.no_cpu_baseline = args.no_roofline = args.no_extras = args.no_ab = True
     relaunch_under_torchrun(args)
 
     from cape_amd import dist as cdist
@@ -587,7 +624,9 @@ def main():
     elapsed = cdist.max_over_ranks(time.perf_counter() - t0, model.device)
 
     loss = float(runner.losses['loss_g']) if 'loss_g' in runner.losses else float('nan')
-    if world > 1:
+    if args.dump_outputs and rank == 0:
+        dump_outputs(runner, args.dump_outputs)
+    if world > 1 and args.full:
         # what the exchange costs the step: the same split step (graphs A1 / A2 / B) with the collectives switched off, AFTER the
         # timed region (the replicas drift apart from here on; nothing below reads the variables)
         hook.enabled = False

@@ -79,7 +79,7 @@ def test_bench_gpus2_without_torchrun_launches_two_ranks():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--no-cpu-baseline", "--no-extras", "--no-ab", "--no-roofline"], env=env, stdout=subprocess.PIPE,
+                        "--full", "--no-cpu-baseline", "--no-extras", "--no-ab", "--no-roofline"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     lines = [l for l in r.stdout.decode().splitlines() if l.startswith('{"metric"')]

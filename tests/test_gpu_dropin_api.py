@@ -201,8 +201,8 @@ def test_fit_runs_the_graph_runner_and_matches_eager_train_steps(tmp_path, mesh_
 
 
 def test_reference_demo_trace_on_device(tmp_path, mesh_ops):
-    """The device half of tests/test_reference_entry_script.py: the call trace that the reference's UNMODIFIED
-    run_simple_demo.py produced against cape_amd (constructor keywords, build_graph / encode_only_condition / decode calls and
+    """The device half of tests/test_reference_entry_script.py::test_run_simple_demo_trace_fits_the_host_side: the call trace
+    that the reference's UNMODIFIED run_simple_demo.py produced against cape_amd (constructor keywords, build_graph / encode_only_condition / decode calls and
     every array the script handed over; committed as tests/golden/run_simple_demo_trace.npz) replayed on the real model, followed
     by the demo's own post-processing (demos.py:397-407) down to the .obj files."""
     import json
@@ -260,7 +260,7 @@ def test_reference_demo_trace_on_device(tmp_path, mesh_ops):
 
 
 def test_reference_main_train_trace_on_device(tmp_path, mesh_ops):
-    """The device half of tests/test_reference_entry_script.py::test_main_train_unmodified: the call trace the reference's
+    """The device half of tests/test_reference_entry_script.py::test_main_train_trace_fits_the_host_side: the call trace the reference's
     UNMODIFIED ``main.py --mode train`` produced against cape_amd (committed as tests/golden/main_train_trace.npz) replayed on
     the real model -- constructor keywords, build_graph('train'), a REAL fit over the same synthetic BodyData (one epoch: the
     adversarial step through the captured HIP graph, validation, checkpoint), build_graph('demo') restoring that checkpoint,

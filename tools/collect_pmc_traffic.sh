@@ -14,5 +14,5 @@ for pass in "fetch:FETCH_SIZE" "write:WRITE_SIZE"; do
   DBP=$(ls /tmp/prof_$name/*.db /tmp/prof_$name/*/*.db 2>/dev/null | head -1)
   python $R/tools/pmc_summary.py $DBP $O/pmc_$name.json
 done
-if [ "${2:-}" = "gan" ]; then python $R/bench.py --gan --no-cpu-baseline > $O/${TAG}_bench_gan.json 2>> $O/${TAG}_bench.err; fi
+if [ "${2:-}" = "gan" ]; then python $R/bench.py --full --gan --no-cpu-baseline > $O/${TAG}_bench_gan.json 2>> $O/${TAG}_bench.err; fi
 ls -la $O | tail -5

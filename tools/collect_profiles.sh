@@ -8,12 +8,12 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python $R/bench.py > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
-python $R/bench.py --gan --no-cpu-baseline --no-ab --no-extras > $O/${TAG}_bench_gan.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+python $R/bench.py --full --gan --no-cpu-baseline --no-ab --no-extras > $O/${TAG}_bench_gan.json 2>> $O/${TAG}_bench.err
 # BASELINE configs[4] (bf16 storage, one GPU's shard of 16), configs[3] (nz18 group-norm generator + discriminator, batch 32)
-python $R/bench.py --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_bf16.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --config CAPE_nz18_pose24_clotype8_male --gan --batch 32 --no-cpu-baseline --no-ab --no-extras > $O/${TAG}_bench_nz18_gan_b32.json 2>> $O/${TAG}_bench.err
-python $R/bench.py --config CAPE_nz18_pose24_clotype8_male --batch 16 --no-cpu-baseline --no-ab --no-extras > $O/${TAG}_bench_nz18_cvae_b16.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --dtype bf16 --no-cpu-baseline > $O/${TAG}_bench_bf16.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --config CAPE_nz18_pose24_clotype8_male --gan --batch 32 --no-cpu-baseline --no-ab --no-extras > $O/${TAG}_bench_nz18_gan_b32.json 2>> $O/${TAG}_bench.err
+python $R/bench.py --full --config CAPE_nz18_pose24_clotype8_male --batch 16 --no-cpu-baseline --no-ab --no-extras > $O/${TAG}_bench_nz18_cvae_b16.json 2>> $O/${TAG}_bench.err
 python $R/bench.py --host-inputs --no-cpu-baseline --no-roofline > $O/${TAG}_bench_host_inputs.json 2>> $O/${TAG}_bench.err
 rm -rf /tmp/prof_ks && rocprofv3 --kernel-trace --stats -d /tmp/prof_ks -o r -- python $R/bench.py --no-cpu-baseline --no-roofline --no-ab --no-extras --steps 20 --warmup 3 > $O/${TAG}_bench_under_rocprof.json 2>/dev/null
 DB=$(ls /tmp/prof_ks/*.db /tmp/prof_ks/*/*.db 2>/dev/null | head -1)
@@ -32,7 +32,7 @@ python $R/tools/hbm_bw_table.py $O/${TAG}_pmc_summary.json $O/${TAG}_bench_kerne
 ls -la $O | tail -15
 bash $R/tools/collect_config1.sh $TAG
 cd $R
-CAPE_DIST_BACKEND=gloo CAPE_FORCE_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 4 --warmup 1 --no-roofline > $O/${TAG}_bench_2rank_1gpu.json 2>> $O/${TAG}_bench.err
+CAPE_DIST_BACKEND=gloo CAPE_FORCE_DEVICE=0 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --steps 4 --warmup 1 --no-roofline > $O/${TAG}_bench_2rank_1gpu.json 2>> $O/${TAG}_bench.err
 tail -c 400 $O/${TAG}_bench_2rank_1gpu.json
 make -C $R/tools/ubench > /dev/null 2>&1
 (cd $R/tools/ubench && ./mfma_peak) > $O/${TAG}_ubench_mfma_peak.txt 2>&1

@@ -1509,3 +1509,48 @@ class CAPE(base_model):
                     x = self.decoder_cond_vert(bz, self._dev(bc), self._dev(bc2), use_res_block=self.use_res_block_dec)
                 recs.append(x[:end - begin].cpu().numpy())
         return np.concatenate(recs, 0)
+
+    def decode_posed(self, data, cond, cond2, pose, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None):
+        """``decode`` followed by demos.py's posing step (:155-161 / :207-213 dress, :267-283 / :312-326 SMPL forward), on
+        the device per padded batch: decoder -> cape_smpl_dress -> cape_smpl_joints -> cape_smpl_skin.  ``pose`` [size, 72]
+        or [1, 72] (one pose for every sample), ``transl`` likewise or None; ``body_model`` a ``cape_amd.smpl.SMPL`` (or the
+        object ``cape_amd.smpl.create`` returns); ``minimal_shape`` defaults to the template mesh.  Batching, padding and the
+        one-condition-many-samples rule are decode's.  Returns (posed, clothed_unposed) [size, V, 3] float32."""
+        from . import smpl as smpl_mod
+        body = getattr(body_model, 'model', body_model)
+        size = data.shape[0]
+        V = body.V
+        pose = np.asarray(pose, dtype=np.float32).reshape(-1, 3 * body.J)
+        if pose.shape[0] not in (1, size):
+            raise ValueError("pose: %d rows for %d samples" % (pose.shape[0], size))
+        if transl is not None:
+            transl = np.asarray(transl, dtype=np.float32).reshape(-1, 3)
+            if transl.shape[0] not in (1, size):
+                raise ValueError("transl: %d rows for %d samples" % (transl.shape[0], size))
+        rows = lambda a, b, e: None if a is None else (np.repeat(a, e - b, 0) if a.shape[0] == 1 else a[b:e])
+        dressing = smpl_mod._DressArrays(mean, std, clothing_idx, self.verts_ref if minimal_shape is None else minimal_shape,
+                                         V, self.device)
+        self._get_session()
+        self._begin_pass()
+        posed, clothed = [], []
+        with torch.no_grad():
+            for begin in range(0, size, self.batch_size):
+                end = min(begin + self.batch_size, size)
+                bz = self._dev(self._pad(data, begin, end, data.shape[1:]))
+                bc = np.zeros((self.batch_size, cond.shape[1]))
+                bc2 = np.zeros((self.batch_size, cond2.shape[1]))
+                if cond.shape[0] == 1:      # one condition, many z samples (reference :1155-1158)
+                    bcond, econd = 0, self.batch_size
+                else:
+                    bcond, econd = begin, end
+                bc[:end - begin] = cond[bcond:econd]
+                bc2[:end - begin] = cond2[bcond:econd]
+                with self.variable_scope('generator'):
+                    x = self.decoder_cond_vert(bz, self._dev(bc), self._dev(bc2), use_res_block=self.use_res_block_dec)
+                x = x[:end - begin].float().contiguous()
+                T = dressing(x)
+                bt = rows(transl, begin, end)
+                vo, _ = body.forward(T, self._dev(rows(pose, begin, end)), None, None if bt is None else self._dev(bt))
+                posed.append(vo.cpu().numpy())
+                clothed.append(T.cpu().numpy())
+        return np.concatenate(posed, 0), np.concatenate(clothed, 0)

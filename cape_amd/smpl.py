@@ -1,0 +1,294 @@
+"""SMPL posing on the device: the step after ``decode`` that turns CAPE's rest-pose clothing displacements into posed clothed
+bodies (reference demos.py:155-161, 207-213 and :249-331, which go through ``smplx`` one mesh at a time on the CPU).
+
+  load_smpl_model(path)      an SMPL model file (.npz, or a chumpy-free .pkl) -> ``SMPL`` with its arrays on the device
+  SMPL.forward(...)          batched forward pass on torch device tensors (libcape_hip.so cape_smpl_joints / cape_smpl_skin)
+  SMPL.pose(...)             the same on numpy arrays
+  dress(...)                 de-normalise + clothing mask + minimal body (cape_smpl_dress)
+  create(...), body_models   an ``smplx``-compatible factory: with a one-line ``smplx.py`` in the reference checkout
+                             (``from cape_amd.smpl import body_models``) demos.py poses through the device unchanged
+
+The joints are regressed from the rest body the caller passes -- in demos.py the CLOTHED body, because it overwrites the
+model's ``v_template`` with it.  There is no CPU fallback and no gradient: inputs that require grad are refused.
+"""
+import ctypes as C
+import os
+import pickle
+import types
+
+import numpy as np
+import torch
+
+from . import _lib
+
+MAX_JOINTS = 64
+
+
+def _stream():
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def _p(t):
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+# ---- model files ----------------------------------------------------------------------------------------------------------
+def _dense(a):
+    return a.toarray() if hasattr(a, "toarray") else np.asarray(a)
+
+
+def read_model_file(path):
+    """The arrays of an SMPL model file as a dict of numpy arrays / scipy sparse matrices (SMPL key names)."""
+    if path.endswith(".npz"):
+        with np.load(path, allow_pickle=False) as z:
+            d = {k: z[k] for k in z.files}
+        if "J_regressor_data" in d:            # a sparse J_regressor saved as its CSR parts
+            import scipy.sparse as sp
+            d["J_regressor"] = sp.csr_matrix((d.pop("J_regressor_data"), d.pop("J_regressor_indices"),
+                                              d.pop("J_regressor_indptr")), shape=tuple(d.pop("J_regressor_shape")))
+        return d
+    with open(path, "rb") as fh:
+        try:
+            d = pickle.load(fh, encoding="latin1")
+        except ModuleNotFoundError as e:
+            if "chumpy" in str(e):
+                raise ValueError(
+                    "%s stores its arrays as chumpy objects, which cape_amd does not read. Convert it once where chumpy is "
+                    "installed: load it with pickle (encoding='latin1'), replace every chumpy array x by np.array(x), and "
+                    "pickle the dict again (or np.savez it with the same keys)." % path) from None
+            raise
+    return dict(d)
+
+
+def _model_arrays(d, num_betas):
+    for k in ("v_template", "J_regressor", "weights", "posedirs", "shapedirs", "kintree_table", "f"):
+        if k not in d:
+            raise KeyError("SMPL model: missing array %r" % k)
+    vt = np.asarray(d["v_template"], dtype=np.float64)
+    V = vt.shape[0]
+    parents = np.asarray(d["kintree_table"])[0].astype(np.int64)
+    parents[parents == 4294967295] = -1                  # the files store parents[0] = -1 as uint32
+    J = len(parents)
+    if not 1 <= J <= MAX_JOINTS:
+        raise ValueError("SMPL model: %d joints (1..%d supported)" % (J, MAX_JOINTS))
+    if parents[0] != -1 or any(not 0 <= parents[j] < j for j in range(1, J)):
+        raise ValueError("SMPL model: the kinematic tree is not parent-ordered (parents[j] < j); reordering a file's joints "
+                         "is not supported")
+    import scipy.sparse as sp
+    jreg = sp.csr_matrix(d["J_regressor"], dtype=np.float64)
+    jreg.sum_duplicates()
+    jreg.sort_indices()
+    W = _dense(d["weights"]).astype(np.float64)
+    posedirs = np.asarray(d["posedirs"], dtype=np.float64)
+    shapedirs = np.asarray(_dense(d["shapedirs"]), dtype=np.float64)
+    if (jreg.shape != (J, V) or W.shape != (V, J) or vt.shape != (V, 3) or posedirs.shape != (V, 3, 9 * (J - 1))
+            or shapedirs.ndim != 3 or shapedirs.shape[:2] != (V, 3)):
+        raise ValueError("SMPL model: inconsistent array shapes")
+    B = min(int(num_betas), shapedirs.shape[2])
+    return dict(v_template=vt, J_regressor=jreg, weights=W, posedirs=posedirs, shapedirs=shapedirs[:, :, :B],
+                parents=parents, faces=np.asarray(d["f"]).astype(np.int64), J=J, V=V, B=B)
+
+
+def load_smpl_model(path, num_betas=10, device=None):
+    """Read an SMPL model file (.npz with the SMPL key names, or a chumpy-free .pkl) and upload it: ``SMPL``."""
+    return SMPL(read_model_file(path), num_betas=num_betas, device=device)
+
+
+class SMPL(object):
+    """An SMPL body model with its arrays in the device layouts of include/cape_hip.h ("SMPL posing")."""
+
+    def __init__(self, arrays, num_betas=10, device=None):
+        m = _model_arrays(arrays, num_betas)
+        self._device = device
+        self.J, self.V, self.num_betas = m["J"], m["V"], m["B"]
+        self.parents = m["parents"]
+        self.faces = m["faces"]
+        self.v_template_np = m["v_template"]
+        self.host = m                                     # float64 host arrays (tests, the compat object)
+        J, V = self.J, self.V
+        jreg = m["J_regressor"]
+        rp, ci = jreg.indptr.astype(np.int32), jreg.indices.astype(np.int32)
+        _lib.check(_lib.lib.cape_csr_validate(J, V, int(jreg.nnz), rp.ctypes.data_as(C.c_void_p),
+                                              ci.ctypes.data_as(C.c_void_p)), "SMPL J_regressor")
+        # skinning weights: ELL of the nonzeros in increasing joint order, padded with (joint 0, 0.0); planar [W][V]
+        nz = m["weights"] != 0
+        width = max(1, int(nz.sum(1).max()))
+        ell_j = np.zeros((width, V), np.int32)
+        ell_w = np.zeros((width, V), np.float32)
+        for v in range(V):
+            js = np.flatnonzero(nz[v])
+            ell_j[:len(js), v] = js
+            ell_w[:len(js), v] = m["weights"][v, js]
+        self.ell_width = width
+        # [shapedirs | posedirs] planar [K][3][V]: lanes of a wave load consecutive words of one coefficient's plane
+        basis = np.concatenate([m["shapedirs"].transpose(2, 1, 0), m["posedirs"].transpose(2, 1, 0)], 0)
+        jsd = np.einsum("jv,vcb->bjc", jreg.toarray(), m["shapedirs"])          # J_regressor . shapedirs, [B][J][3]
+        self.layouts = dict(rowptr=(rp, np.int32), colidx=(ci, np.int32), vals=(jreg.data, np.float32),
+                            ell_j=(ell_j, np.int32), ell_w=(ell_w, np.float32), basis=(basis, np.float32),
+                            jshapedirs=(jsd, np.float32), v_template=(m["v_template"], np.float32))
+        self._dev = None
+        self._parents_c = (C.c_int32 * J)(*[int(x) for x in self.parents])
+
+    @property
+    def device(self):
+        return self._upload().device
+
+    def _upload(self):
+        """The device arrays, uploaded on first use (a model can be read and inspected without a GPU)."""
+        if self._dev is None:
+            _lib.require_gpu()
+            dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            self._dev = types.SimpleNamespace(device=dev, **{k: torch.as_tensor(np.ascontiguousarray(a, dtype=dt)).to(dev)
+                                                             for k, (a, dt) in self.layouts.items()})
+        return self._dev
+
+    @property
+    def basis_bytes(self):
+        return self.layouts["basis"][0].size * 4
+
+    def forward(self, verts, pose, betas=None, transl=None, out=None):
+        """Pose N meshes.  ``verts`` [N,V,3] or [1,V,3] (one rest body for every pose; None: the template), ``pose`` [N,J*3]
+        axis-angle (joint 0 = global orientation), ``betas`` [N,<=B], ``transl`` [N,3]: float32 tensors on this model's device.
+        Returns (vertices [N,V,3], joints [N,J,3]); with ``out`` = that pair preallocated, nothing synchronises the host, so
+        the call can be captured in a graph."""
+        J, V, d = self.J, self.V, self._upload()
+        if verts is None:
+            verts = d.v_template[None]
+        pose = pose.reshape(pose.shape[0], -1)
+        N = pose.shape[0]
+        for name, t in (("verts", verts), ("pose", pose), ("betas", betas), ("transl", transl)):
+            if t is None:
+                continue
+            if t.requires_grad:
+                raise RuntimeError("cape_amd.smpl: forward only, %s requires grad" % name)
+            if t.dtype != torch.float32 or t.device != d.device or not t.is_contiguous():
+                raise ValueError("cape_amd.smpl: %s must be a contiguous float32 tensor on %s" % (name, d.device))
+        if pose.shape[1] != 3 * J:
+            raise ValueError("pose: %d values per sample, the model has %d joints" % (pose.shape[1], J))
+        if verts.dim() != 3 or verts.shape[1:] != (V, 3) or verts.shape[0] not in (1, N):
+            raise ValueError("verts: [%d or 1, %d, 3] expected, got %s" % (N, V, tuple(verts.shape)))
+        B = 0
+        if betas is not None:
+            betas = betas.reshape(N, -1)
+            B = betas.shape[1]
+            if B > self.num_betas:
+                raise ValueError("betas: %d given, the model keeps %d" % (B, self.num_betas))
+            if B == 0:
+                betas = None
+            elif B < self.num_betas:      # the basis keeps the model's shape rows in front of the pose rows: pad with zeros
+                betas = torch.cat([betas, betas.new_zeros((N, self.num_betas - B))], 1)
+                B = self.num_betas
+        if transl is not None and tuple(transl.shape) not in ((N, 3),):
+            raise ValueError("transl: [%d, 3] expected" % N)
+        if out is None:
+            out = (torch.empty((N, V, 3), dtype=torch.float32, device=d.device),
+                   torch.empty((N, J, 3), dtype=torch.float32, device=d.device))
+        vo, jo = out
+        if tuple(vo.shape) != (N, V, 3) or tuple(jo.shape) != (N, J, 3) or not (vo.is_contiguous() and jo.is_contiguous()):
+            raise ValueError("out: contiguous [N,V,3] and [N,J,3] float32 tensors expected")
+        K = B + 9 * (J - 1)
+        coef = torch.empty((N, K), dtype=torch.float32, device=d.device)
+        G = torch.empty((N, J, 12), dtype=torch.float32, device=d.device)
+        tss = 0 if verts.shape[0] == 1 else 3 * V
+        s = _stream()
+        _lib.check(_lib.lib.cape_smpl_joints(_p(verts), tss, _p(d.rowptr), _p(d.colidx), _p(d.vals), _p(pose),
+                                             _p(betas), B, _p(d.jshapedirs), _p(transl), self._parents_c, J, V, N,
+                                             _p(coef), _p(G), _p(jo), s), "cape_smpl_joints")
+        # no betas: the basis starts past the model's shape rows
+        basis = C.c_void_p(d.basis.data_ptr() + 4 * 3 * V * (self.num_betas - B))
+        _lib.check(_lib.lib.cape_smpl_skin(_p(verts), tss, basis, K, _p(coef), _p(G), _p(d.ell_j), _p(d.ell_w),
+                                           self.ell_width, _p(transl), J, V, N, _p(vo), 3 * V, s), "cape_smpl_skin")
+        return vo, jo
+
+    __call__ = forward
+
+    def pose(self, verts, pose, betas=None, transl=None):
+        """numpy in, numpy out: (vertices [N,V,3], joints [N,J,3]) float32."""
+        t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32).to(self.device)
+        with torch.no_grad():
+            pose = np.asarray(pose).reshape(-1, 3 * self.J)
+            verts = None if verts is None else np.asarray(verts).reshape(-1, self.V, 3)
+            vo, jo = self.forward(t(verts), t(pose), t(betas), t(transl))
+            return vo.cpu().numpy(), jo.cpu().numpy()
+
+
+# ---- dress ---------------------------------------------------------------------------------------------------------------
+class _DressArrays(object):
+    """mean / std / minimal [V,3] and the clothing mask [V] on the device, uploaded once."""
+
+    def __init__(self, mean, std, clothing_idx, minimal_shape, V, device):
+        dev = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+        mask = np.zeros(V, np.float32)
+        mask[np.asarray(clothing_idx, dtype=np.int64)] = 1.0
+        self.mean, self.std = dev(np.reshape(mean, (V, 3))), dev(np.reshape(std, (V, 3)))
+        self.minimal, self.mask = dev(np.reshape(minimal_shape, (V, 3))), dev(mask)
+        self.V = V
+
+    def __call__(self, disp, out=None):
+        N, V = disp.shape[0], self.V
+        if disp.dtype != torch.float32 or not disp.is_contiguous() or tuple(disp.shape[1:]) != (V, 3):
+            raise ValueError("disp: contiguous float32 [N, %d, 3] expected" % V)
+        if out is None:
+            out = torch.empty((N, V, 3), dtype=torch.float32, device=disp.device)
+        _lib.check(_lib.lib.cape_smpl_dress(_p(disp), 3 * V, _p(self.mean), _p(self.std), _p(self.mask), _p(self.minimal),
+                                            _p(out), 3 * V, N, V, _stream()), "cape_smpl_dress")
+        return out
+
+
+def dress(disp, mean, std, clothing_idx, minimal_shape):
+    """demos.py:155-161: ``minimal_shape + mask(clothing_idx) * (disp * std + mean)`` for a device tensor ``disp`` [N,V,3];
+    the other arguments are host arrays.  Returns the clothed rest bodies [N,V,3] on the device."""
+    return _DressArrays(mean, std, clothing_idx, minimal_shape, disp.shape[1], disp.device)(disp)
+
+
+# ---- smplx-compatible factory (demos.py:22-24, 267-283, 312-326) -------------------------------------------------------------
+class _Output(object):
+    def __init__(self, vertices, joints):
+        self.vertices = vertices
+        self.joints = joints
+
+
+class SMPLLayer(object):
+    """What demos.py touches of an ``smplx.SMPL``: writable CPU float32 ``v_template`` [V,3], ``body_pose`` [1,3(J-1)],
+    ``global_orient`` [1,3], ``transl`` [1,3], ``betas`` [1,B] and ``faces``; calling it poses on the device and returns
+    ``.vertices`` [1,V,3] and ``.joints`` [1,J,3].  ``.joints`` holds the J skeleton joints only, not the extra vertex
+    joints smplx appends."""
+
+    def __init__(self, model):
+        self.model = model
+        self.faces = model.faces
+        self.v_template = torch.tensor(model.v_template_np, dtype=torch.float32)
+        self.body_pose = torch.zeros((1, 3 * (model.J - 1)), dtype=torch.float32)
+        self.global_orient = torch.zeros((1, 3), dtype=torch.float32)
+        self.transl = torch.zeros((1, 3), dtype=torch.float32)
+        self.betas = torch.zeros((1, model.num_betas), dtype=torch.float32)
+
+    def __call__(self, betas=None, body_pose=None, global_orient=None, transl=None, **kw):
+        m = self.model
+        d = lambda t, default: (default if t is None else t).detach().to(device=m.device, dtype=torch.float32).contiguous()
+        with torch.no_grad():
+            pose = torch.cat([d(global_orient, self.global_orient).reshape(1, 3),
+                              d(body_pose, self.body_pose).reshape(1, -1)], 1).contiguous()
+            vo, jo = m.forward(d(None, self.v_template)[None], pose, d(betas, self.betas).reshape(1, -1),
+                               d(transl, self.transl).reshape(1, 3))
+        return _Output(vo, jo)
+
+    forward = __call__
+
+
+def create(model_path, model_type="smpl", gender="neutral", ext="pkl", num_betas=10, device=None, **kw):
+    """``smplx.create`` for SMPL: ``model_path`` is a model file, or a folder holding ``smpl/SMPL_<GENDER>.<ext>``."""
+    if model_type.lower() != "smpl":
+        raise ValueError("cape_amd.smpl.create: only model_type='smpl' is supported, not %r" % model_type)
+    path = model_path
+    if os.path.isdir(path):
+        sub = os.path.join(path, model_type.lower())
+        path = os.path.join(sub if os.path.isdir(sub) else path, "SMPL_%s.%s" % (gender.upper(), ext))
+    if not os.path.exists(path):
+        raise FileNotFoundError("SMPL model file not found: %s" % path)
+    return SMPLLayer(load_smpl_model(path, num_betas=num_betas, device=device))
+
+
+class body_models(object):
+    """``smplx.body_models`` namespace: ``body_models.create(...)`` as demos.py:22 calls it."""
+    create = staticmethod(create)

@@ -49,6 +49,9 @@
  *                       lib/models.py:357-375 L1 reconstruction + lib/losses.py:9-25 edge loss
  *                       and their gradients w.r.t. the prediction.
  *   cape_csr_validate   host-side structural check of an operator before upload.
+ *   cape_smpl_dress / cape_smpl_joints / cape_smpl_skin
+ *                       demos.py:155-161, 207-213 (de-normalise, clothing mask, + minimal body) and the SMPL forward pass
+ *                       demos.py:267-283, 312-326 run through smplx (the model demos.py:22 creates), for a batch of meshes.
  */
 #ifndef CAPE_HIP_H
 #define CAPE_HIP_H
@@ -59,7 +62,7 @@
 extern "C" {
 #endif
 
-#define CAPE_ABI_VERSION 13
+#define CAPE_ABI_VERSION 14
 #define CAPE_MAX_SRC 8
 
 /* error codes (negative = argument error; positive values are hipError_t) */
@@ -791,6 +794,44 @@ int cape_cheb_fused_bwd(const float *x, int64_t x_sample_stride, int32_t ldx, co
                         int32_t rmax, void *workspace, int64_t workspace_bytes, void *stream);
 /* diagnostic: device buffer of >= 64 uint64 stamped with s_memtime at the forward kernel's phase boundaries (NULL = off) */
 int cape_cheb_fused_debug_timestamps(void *ts);
+
+/*
+ * SMPL posing (cape_amd/csrc/smpl/smpl.hip) -- the last step of demos.py (:155-161, 207-213 and :267-283, 312-326: the
+ * decoder output de-normalised, masked to the clothing vertices, added to the minimal body, then posed by the SMPL forward
+ * pass of smplx, one mesh per call on the CPU), for N meshes at once.  Forward only.  Model arrays in the device layouts
+ * cape_amd.smpl builds at load (SMPL file layouts: v_template [V,3], J_regressor [J,V], weights [V,J],
+ * posedirs [V,3,9(J-1)], shapedirs [V,3,B]):
+ *   jreg rowptr / colidx / vals   J_regressor as CSR (J rows, columns < V, checked at load)
+ *   jshapedirs [B][J][3]          J_regressor . shapedirs, so that joints need no pass over the shape basis
+ *   basis      [K][3][V]          planar [shapedirs[:, :, :B] | posedirs] coefficient-major, K = B + 9(J-1)
+ *   ell_joint / ell_weight [W][V] each vertex's nonzero skinning weights in increasing joint order, padded with (0, 0.0)
+ *   parents    HOST int32 [J]     parents[0] = -1, 0 <= parents[j] < j: passed by value in the launch
+ * Per sample n, with rest vertices T[n] (T_sample_stride = 0 broadcasts one body), axis-angle pose [N][J][3] (joint 0 =
+ * global orientation), betas [N][B] (B = 0: none), transl [N][3] (NULL: none):
+ *   Jn = J_regressor . T[n] + jshapedirs . betas   (joints from the CLOTHED rest body, as demos.py gets them by writing the
+ *                                                    clothed body into v_template)
+ *   R_j = Rodrigues(pose_j) (series below |pose_j|^2 = 1e-6: exactly I at 0); coef[n] = [betas | pf],
+ *   pf[(j-1)*9 + 3r + c] = R_j[r][c] - delta_rc;  A_0 = [R_0 | J_0], A_j = A_parent(j) [R_j | J_j - J_parent(j)]
+ *   G[n][j] = [A_j.rot | A_j.t - A_j.rot J_j] (3 rows of 4);  joints[n][j] = A_j.t + transl
+ *   out[n][v] = (sum_j W[v][j] G[n][j]) [T[n][v] + sum_k coef[n][k] basis[k][:][v]; 1] + transl
+ * Joint regression reduces each row in a fixed order, skinning sums each vertex's weights in increasing joint order:
+ * deterministic, no atomics.  Errors: CAPE_EINVAL for NULL operands, sizes, J outside 1..64; CAPE_ERANGE for a tree that
+ * is not parent-ordered (parents[0] != -1, or parents[j] outside [0, j) for j >= 1).
+ */
+/* T[n, v, :] = minimal[v, :] + mask[v] * (disp[n, v, :] * std[v, :] + mean[v, :]); mean / std / minimal [V][3], mask [V] */
+int cape_smpl_dress(const float *disp, int64_t disp_sample_stride, const float *mean, const float *std_, const float *mask,
+                    const float *minimal, float *T, int64_t T_sample_stride, int32_t N, int32_t V, void *stream);
+/* one workgroup per sample: coef [N][B + 9(J-1)], G [N][J][12], joints [N][J][3] (NULL: not written) */
+int cape_smpl_joints(const float *T, int64_t T_sample_stride, const int32_t *jreg_rowptr, const int32_t *jreg_colidx,
+                     const float *jreg_vals, const float *pose, const float *betas, int32_t B, const float *jshapedirs,
+                     const float *transl, const int32_t *parents, int32_t J, int32_t V, int32_t N, float *coef, float *G,
+                     float *joints, void *stream);
+/* samples per skinning workgroup for K coefficients and J joints (up to 16, each reads the basis once), or CAPE_EINVAL */
+int cape_smpl_skin_tile(int32_t K, int32_t J);
+/* one thread per vertex; basis may start past the shape rows (betas unused: K = 9(J-1), basis + 3 * B * V) */
+int cape_smpl_skin(const float *T, int64_t T_sample_stride, const float *basis, int32_t K, const float *coef, const float *G,
+                   const int32_t *ell_joint, const float *ell_weight, int32_t ell_width, const float *transl, int32_t J,
+                   int32_t V, int32_t N, float *out, int64_t out_sample_stride, void *stream);
 
 #ifdef __cplusplus
 }

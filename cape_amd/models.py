@@ -73,11 +73,15 @@ class base_model(object):
         # data/edges_smpl.npy next to lib/); a CAPE checkout at project_dir wins, else the pack.
         self.verts_ref, self.vpe = self._load_template()
 
-        if loss_mask == 'binary':
-            # reference quirk C5: wrong directory + 1-D mask indexed as 2-D -> the feature never
-            # worked upstream; refuse explicitly instead of guessing.
-            raise NotImplementedError("loss_mask='binary' is broken in the reference (SURVEY C5)")
-        self.loss_mask = 1.0
+        # loss_mask (reference :47-52): 'binary' reads the shipped per-vertex weights; any other string or None is the
+        # reference's else branch.  _loss_mask_w: the [V, 3] float32 weights, None without a mask.
+        self._loss_mask_w = self._resolve_loss_mask(loss_mask)
+        if self._loss_mask_w is None:
+            self.loss_mask = 1.0
+        else:
+            # what the reference meant to build (:49-50): the weights repeated over the batch
+            self.loss_mask = np.repeat(self._loss_mask_w[np.newaxis], batch_size, 0)
+            self._loss_mask_sum = float(self._loss_mask_w.astype(np.float64).sum())      # one sample's sum of weights
 
         self.nz = nz
         self.cond_dim = cond_dim
@@ -126,6 +130,33 @@ class base_model(object):
             return np.asarray(verts, dtype=np.float64), np.load(edg)
         pack = load_pack()
         return pack['template_verts'], pack['edges_smpl']
+
+    def _resolve_loss_mask(self, loss_mask):
+        """[V, 3] float32 weights of the reconstruction loss, or None.  'binary': <project_dir>/data/loss_mask_binary.npy (where
+        the reference ships it), else <project_dir>/lib/data/loss_mask_binary.npy (the path its code names, quirk C5).  An
+        array of shape (V,), (V, 1) or (V, 3): custom weights, non-negative and finite, not all zero."""
+        if loss_mask is None or isinstance(loss_mask, str):
+            if loss_mask != 'binary':
+                return None
+            paths = [os.path.join(self.project_dir, 'data', 'loss_mask_binary.npy'),
+                     os.path.join(self.project_dir, 'lib', 'data', 'loss_mask_binary.npy')]
+            found = [q for q in paths if os.path.exists(q)]
+            if not found:
+                raise FileNotFoundError("loss_mask='binary': neither %s nor %s exists" % tuple(paths))
+            loss_mask = np.load(found[0])
+        V = self.input_num_verts
+        w = np.asarray(loss_mask, dtype=np.float64)
+        if w.shape == (V,):
+            w = w[:, np.newaxis]
+        if w.shape not in ((V, 1), (V, 3)):
+            raise ValueError("loss_mask: shape %s, expected (%d,), (%d, 1) or (%d, 3)" % (w.shape, V, V, V))
+        if not np.isfinite(w).all():
+            raise ValueError("loss_mask: non-finite weights")
+        if (w < 0).any():
+            raise ValueError("loss_mask: negative weights")
+        if not (w > 0).any():
+            raise ValueError("loss_mask: all weights are zero")
+        return np.ascontiguousarray(np.broadcast_to(w, (V, 3)), dtype=np.float32)
 
     # ---- variable store (TF-style scoped names) ------------------------------------------------
     class _ScopeCtx(object):
@@ -771,13 +802,35 @@ class CAPE(base_model):
                               torch.tensor(vidx, dtype=torch.int32, device=d))
         return self._edge_dev
 
+    def _loss_mask_dev(self):
+        """The mask's [V, 3] weights on the device, made once: a captured step keeps pointing at this tensor."""
+        if not hasattr(self, '_loss_mask_t'):
+            self._loss_mask_t = torch.tensor(self._loss_mask_w, dtype=torch.float32, device=self.device)
+        return self._loss_mask_t
+
     def loss_terms(self, g_outputs, g_gt, z_mean, z_logvar):
         """recon / latent / edge / fc-regularisation terms and their weighted sum (no GAN term)."""
         out = {}
         lat = self._latent_term(z_mean, z_logvar)
         reg = self._fc_regulariser()
         out['latent'], out['fc_reg_g'] = lat, reg
-        if self.which_loss == 'l1' and g_outputs.shape[-1] == 3:
+        if self._loss_mask_w is not None and g_outputs.shape[-1] == 3:
+            # loss_mask (reference :357-369): every loss kind through the weighted kernel, sum w * l / sum w; latent and
+            # regulariser are folded in under the same conditions as in the l1 branch below
+            vr, ed, vptr, vidx = self._edge_tables()
+            scalar = lambda t: torch.is_tensor(t) and t.dim() == 0 and t.is_cuda and t.dtype == torch.float32
+            reg_ok = (scalar(reg) and not reg.requires_grad) if torch.is_tensor(reg) else float(reg) == 0.0
+            kind = self.which_loss if self.which_loss in ('l1', 'huber') else 'l2'       # :367 else: mean_squared_error
+            args = (g_outputs, g_gt, vr, ed, vptr, vidx, self._loss_mask_dev(), self._loss_mask_sum, kind,
+                    float(self.lambda_l1), float(self.lambda_edge))
+            if g_outputs.is_cuda and scalar(lat) and reg_ok:
+                total, parts = ops.MaskedReconEdgeLossFn.apply(*args, lat, float(self.lambda_latent),
+                                                               reg if torch.is_tensor(reg) else None)
+                out['recon'], out['edge'], out['total_no_gan'] = parts[0], parts[1], total
+                return out
+            total_re, parts = ops.MaskedReconEdgeLossFn.apply(*args)
+            out['recon'], out['edge'] = parts[0], parts[1]
+        elif self.which_loss == 'l1' and g_outputs.shape[-1] == 3:
             vr, ed, vptr, vidx = self._edge_tables()
             # the latent term and the regulariser value join the weighted sum INSIDE the loss kernel when they are device
             # scalars already (the fused sampling / KL op; the bucket path's detached regulariser): no element-wise launches

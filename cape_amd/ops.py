@@ -2096,6 +2096,63 @@ class ReconEdgeLossFn(torch.autograd.Function):
         return (dpred if unit else dpred * gtotal), None, None, None, None, None, None, None, ga, None, None
 
 
+MASKED_LOSS_KIND = {'l1': 0, 'huber': 1, 'l2': 2}
+
+
+class MaskedReconEdgeLossFn(torch.autograd.Function):
+    """ReconEdgeLossFn with the reference's loss_mask (lib/models.py:47-52, 357-369): recon = sum w * l(pred - gt) / sum w,
+    l the l1 / huber / l2 loss of ``kind`` and w the per-vertex weights ``weights`` [M, 3] (fp32, device) broadcast over the
+    batch -- TF's Reduction.MEAN of the weighted loss.  ``weight_sum``: the host's sum of ``weights`` (one sample); the
+    kernel is handed 1 / (N * weight_sum).  Same outputs, same term_a / term_b folding, same gradient shortcut."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, verts_ref, edges, vptr, vidx, weights, weight_sum, kind, w_recon, w_edge, term_a=None, w_a=0.0,
+                term_b=None):
+        _lib.require_gpu()
+        gt = gt.contiguous()
+        N, M, _ = pred.shape
+        if pred.stride(2) != 1 or pred.stride(1) < 3 or (N > 1 and pred.stride(0) != M * pred.stride(1)):
+            pred = pred.contiguous()
+        ldp = int(pred.stride(1)) if M > 1 else 3
+        E = edges.shape[0]
+        assert weights.shape == (M, 3) and weights.dtype == torch.float32 and weights.is_contiguous() and weights.device == pred.device
+        code = MASKED_LOSS_KIND[kind]
+        if L1_SIGN_TRACE is not None and code == 0 and w_recon != 0.0:
+            L1_SIGN_TRACE.append(torch.sign(pred.detach() - gt).cpu())
+        need = lib.cape_masked_recon_edge_workspace_bytes(N, M, E)
+        ws = torch.empty((need + 3) // 4, device=pred.device, dtype=torch.float32)
+        out = torch.empty(2, device=pred.device, dtype=torch.float32)
+        total = torch.empty((), device=pred.device, dtype=torch.float32)
+        dpred = alloc_act(N, M, 3, pred.device, zero=False)
+        ldd = int(dpred.stride(1))
+        for t in (term_a, term_b):
+            assert t is None or (t.dim() == 0 and t.dtype == torch.float32 and t.device == pred.device)
+        inv = 1.0 / (N * float(weight_sum))
+        _log_launch("masked_recon_edge_loss", 0, N * (E * 24 + M * 36) + M * 12,
+                    lambda: check(lib.cape_masked_recon_edge_loss_fwd_bwd(_ptr(pred), ldp, _ptr(gt), _ptr(verts_ref), _ptr(edges),
+                                                                          _ptr(vptr), _ptr(vidx), N, M, E, _ptr(weights), code, inv,
+                                                                          float(w_recon), float(w_edge), _ptr(out), _ptr(total),
+                                                                          _ptr(term_a), float(w_a), _ptr(term_b), _ptr(dpred), ldd,
+                                                                          _ptr(ws), need, _stream()),
+                                  "cape_masked_recon_edge_loss_fwd_bwd"))
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(dpred)
+        ctx.w_a = float(w_a) if term_a is not None else None
+        ctx.mark_non_differentiable(out)
+        return total, out
+
+    @staticmethod
+    def backward(ctx, gtotal, _gout):
+        (dpred,) = ctx.saved_tensors
+        if gtotal is None:
+            return (None,) * 14
+        unit = UNIT_GRAD is not None and gtotal.data_ptr() == UNIT_GRAD.data_ptr()
+        ga = None
+        if ctx.w_a is not None and ctx.needs_input_grad[11]:
+            ga = _const_scalar(ctx.w_a, dpred.device) if unit else gtotal * ctx.w_a
+        return (dpred if unit else dpred * gtotal), None, None, None, None, None, None, None, None, None, None, ga, None, None
+
+
 class GanLossFn(torch.autograd.Function):
     """(lambda * gan_g, lambda * gan_d, [gan_g, gan_d]) from the discriminator's logits (lib/models.py:381-390,397):
     sigmoid cross entropy with smoothed labels, both means and both gradients in ONE launch (csrc/loss.hip gan_bce_kernel)

@@ -48,6 +48,9 @@
  *   cape_recon_edge_loss_fwd_bwd
  *                       lib/models.py:357-375 L1 reconstruction + lib/losses.py:9-25 edge loss
  *                       and their gradients w.r.t. the prediction.
+ *   cape_masked_recon_edge_loss_fwd_bwd
+ *                       lib/models.py:47-52, 357-369 loss_mask: the per-vertex weighted l1 / huber / l2 reconstruction
+ *                       loss (TF Reduction.MEAN) + the edge loss, and their gradients w.r.t. the prediction.
  *   cape_csr_validate   host-side structural check of an operator before upload.
  *   cape_smpl_dress / cape_smpl_joints / cape_smpl_skin
  *                       demos.py:155-161, 207-213 (de-normalise, clothing mask, + minimal body) and the SMPL forward pass
@@ -62,7 +65,7 @@
 extern "C" {
 #endif
 
-#define CAPE_ABI_VERSION 14
+#define CAPE_ABI_VERSION 15
 #define CAPE_MAX_SRC 8
 
 /* error codes (negative = argument error; positive values are hipError_t) */
@@ -600,6 +603,26 @@ int cape_recon_edge_loss_fwd_bwd(const float *pred, int32_t ldp, const float *gt
                                  float w_recon, float w_edge, float *loss_out, float *total_out,
                                  const float *term_a, float w_a, const float *term_b, float *dpred,
                                  int32_t ldd, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Weighted reconstruction + edge loss (cape_amd/csrc/loss_mask/masked_loss.hip): the reference's loss_mask option
+ * (lib/models.py:47-52, 357-369), a per-vertex weight passed to tf.losses.absolute_difference / huber_loss /
+ * mean_squared_error as weights= with Reduction.MEAN, which divides the weighted sum by the sum of the broadcast weights:
+ *   d = pred - gt [N, M, 3];  w = weights [M, 3] broadcast over the N samples;  inv_weight_sum = 1 / (N * sum weights)
+ *   loss_out[0] = sum w * l(d) * inv_weight_sum,   l = |d| (loss_kind 0, l1), 0.5 d^2 if |d| <= 0.1 else 0.1 |d| - 0.005
+ *                 (1, huber), d^2 (2, l2)
+ *   d loss_out[0] / d pred = w * l'(d) * inv_weight_sum,  l'(0) = 0 for l1 (TF's sign), l'(d) = clip(d, -0.1, 0.1) for huber
+ * Everything else is cape_recon_edge_loss_fwd_bwd's contract (loss_out[1], total_out, term_a / term_b, dpred, ldp / ldd,
+ * the workspace); the edge value and the edge part of dpred are that entry's bits.  Three launches, fixed-order sums.
+ * CAPE_EINVAL for NULL operands, sizes, loss_kind outside 0..2, inv_weight_sum not finite and > 0.
+ */
+int64_t cape_masked_recon_edge_workspace_bytes(int32_t N, int32_t M, int32_t E);
+int cape_masked_recon_edge_loss_fwd_bwd(const float *pred, int32_t ldp, const float *gt, const float *verts_ref,
+                                        const int32_t *edges, const int32_t *vert_edge_ptr, const int32_t *vert_edge_idx,
+                                        int32_t N, int32_t M, int32_t E, const float *weights, int32_t loss_kind,
+                                        float inv_weight_sum, float w_recon, float w_edge, float *loss_out, float *total_out,
+                                        const float *term_a, float w_a, const float *term_b, float *dpred, int32_t ldd,
+                                        void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * Adversarial losses on the discriminator's logits (lib/models.py:381-390, tf.nn.sigmoid_cross_entropy_with_logits with

@@ -157,6 +157,22 @@ def vertex_edge_table(edges, num_verts):
     return ptr.astype(np.int32), codes.astype(np.int32)
 
 
+def vertex_face_table(faces, num_verts):
+    """CSR over vertices of incident face corners for the face-normal-loss gradient: entry code = 3*f + k, the vertex
+    being corner k of face f.  Every (face, corner) appears exactly once; a vertex's list is sorted by code, so the
+    gradient's summation order is fixed."""
+    faces = np.asarray(faces, dtype=np.int64)
+    F = faces.shape[0]
+    verts = faces.T.reshape(-1)                                   # corner-major: all corner 0, then 1, then 2
+    codes = (3 * np.arange(F)[None, :] + np.arange(3)[:, None]).reshape(-1)
+    order = np.lexsort((codes, verts))                            # by vertex, then by code: each list sorted
+    verts, codes = verts[order], codes[order]
+    ptr = np.zeros(num_verts + 1, dtype=np.int64)
+    np.add.at(ptr, verts + 1, 1)
+    ptr = np.cumsum(ptr)
+    return ptr.astype(np.int32), codes.astype(np.int32)
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Vertex patches for the on-chip Chebyshev recurrence (csrc/cheb_fused.hip; polynomial orders above FUSE_MAX_K, e.g.
 # BASELINE configs[1]: K = 6).  The recurrence T_k = 2 L~ T_{k-1} - T_{k-2} (reference lib/models.py:88-96) couples a

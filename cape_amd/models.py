@@ -26,7 +26,7 @@ import torch
 from . import ops
 from . import _lib
 from . import tf_checkpoint
-from .graph import ConvOperators, HostCSR, is_identity, vertex_edge_table
+from .graph import ConvOperators, HostCSR, is_identity, vertex_edge_table, vertex_face_table
 from .load_data import load_pack
 
 _ACTIVATIONS = ("b1leakyrelu", "b1relu", "b1tanh", "b2relu")
@@ -50,7 +50,8 @@ class base_model(object):
                  optimizer='sgd', decay_steps=None, momentum=0.9, cond_dim=0, nz_cond=0,
                  regularization=0, batch_size=32, seed=123,
                  lambda_recon=1.0, lambda_edge=0.0, lambda_latent=1e-3,
-                 restart=False, name='', loss_mask=None, project_dir=None, device=None, **ignored):
+                 restart=False, name='', loss_mask=None, project_dir=None, device=None, lambda_normal=0.0, faces=None,
+                 **ignored):
         self.seed = seed
         self.input_num_verts = L[0].shape[0]
         self.nn_input_channel = nn_input_channel
@@ -82,6 +83,10 @@ class base_model(object):
             # what the reference meant to build (:49-50): the weights repeated over the batch
             self.loss_mask = np.repeat(self._loss_mask_w[np.newaxis], batch_size, 0)
             self._loss_mask_sum = float(self._loss_mask_w.astype(np.float64).sum())      # one sample's sum of weights
+
+        # lambda_normal: weight of the face-normal loss (lib/losses.py:27-52, unwired in the reference).  0 = off:
+        # no file is read and no table is built.  _faces: the [F, 3] int32 triangles, None when off.
+        self.lambda_normal, self._faces = self._resolve_normal(lambda_normal, faces)
 
         self.nz = nz
         self.cond_dim = cond_dim
@@ -157,6 +162,52 @@ class base_model(object):
         if not (w > 0).any():
             raise ValueError("loss_mask: all weights are zero")
         return np.ascontiguousarray(np.broadcast_to(w, (V, 3)), dtype=np.float32)
+
+    def _resolve_normal(self, lambda_normal, faces):
+        """(lambda_normal, faces [F, 3] int32 or None).  Faces are resolved only for lambda_normal > 0: an explicit array wins,
+        else the 'f' lines of <project_dir>/data/template_mesh.obj."""
+        try:
+            lam = float(lambda_normal)
+        except (TypeError, ValueError):
+            raise ValueError("lambda_normal: %r is not a number" % (lambda_normal,))
+        if not np.isfinite(lam) or lam < 0:
+            raise ValueError("lambda_normal must be finite and >= 0, got %r" % (lambda_normal,))
+        if lam == 0.0:
+            return 0.0, None
+        if self.nn_input_channel != 3:
+            raise ValueError("lambda_normal > 0 needs 3 input channels (vertex coordinates), got %d" % self.nn_input_channel)
+        if faces is None:
+            obj = os.path.join(self.project_dir, 'data', 'template_mesh.obj')
+            if not os.path.exists(obj):
+                raise FileNotFoundError("lambda_normal > 0 needs the template's triangles: pass faces=<(F, 3) integer array> "
+                                        "or provide %s with its 'f' lines" % obj)
+            faces = self._obj_faces(obj)
+        f = np.asarray(faces)
+        if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] < 1:
+            raise ValueError("faces: shape %s, expected (F, 3)" % (f.shape,))
+        if not np.issubdtype(f.dtype, np.integer):
+            raise ValueError("faces: dtype %s, expected integers" % f.dtype)
+        V = self.input_num_verts
+        if f.min() < 0 or f.max() >= V:
+            raise ValueError("faces: vertex indices outside [0, %d)" % V)
+        if ((f[:, 0] == f[:, 1]) | (f[:, 1] == f[:, 2]) | (f[:, 0] == f[:, 2])).any():
+            raise ValueError("faces: a face names the same vertex twice")
+        return lam, np.ascontiguousarray(f, dtype=np.int32)
+
+    @staticmethod
+    def _obj_faces(path):
+        """Triangles of a Wavefront .obj: 'f a b c' lines, 1-based, 'a/b/c' tokens tolerated (the vertex index comes first)."""
+        faces = []
+        with open(path) as fh:
+            for line in fh:
+                if line.startswith('f '):
+                    tok = line.split()[1:]
+                    if len(tok) != 3:
+                        raise ValueError("%s: face line with %d vertices, triangles expected: %r" % (path, len(tok), line.strip()))
+                    faces.append([int(t.split('/')[0]) - 1 for t in tok])
+        if not faces:
+            raise ValueError("%s has no 'f' lines" % path)
+        return np.asarray(faces, dtype=np.int64)
 
     # ---- variable store (TF-style scoped names) ------------------------------------------------
     class _ScopeCtx(object):
@@ -808,8 +859,32 @@ class CAPE(base_model):
             self._loss_mask_t = torch.tensor(self._loss_mask_w, dtype=torch.float32, device=self.device)
         return self._loss_mask_t
 
+    def _face_tables(self):
+        """Faces and the vertex -> incident-corner table on the device, made once: a captured step keeps pointing at them."""
+        if not hasattr(self, '_face_dev'):
+            fptr, fidx = vertex_face_table(self._faces, self.input_num_verts)
+            d = self.device
+            self._face_dev = (torch.tensor(self._faces, dtype=torch.int32, device=d),
+                              torch.tensor(fptr, dtype=torch.int32, device=d),
+                              torch.tensor(fidx, dtype=torch.int32, device=d))
+        return self._face_dev
+
+    def _add_normal(self, out, g_outputs, g_gt):
+        """lambda_normal > 0: out['normal'], and lambda_normal * normal added to out['total_no_gan'] by the loss's own
+        finishing kernel."""
+        faces, fptr, fidx = self._face_tables()
+        total, parts = ops.FaceNormalLossFn.apply(g_outputs, g_gt, self._edge_tables()[0], faces, fptr, fidx,
+                                                  float(self.lambda_normal), out['total_no_gan'])
+        out['normal'], out['total_no_gan'] = parts[0], total
+        return out
+
     def loss_terms(self, g_outputs, g_gt, z_mean, z_logvar):
         """recon / latent / edge / fc-regularisation terms and their weighted sum (no GAN term)."""
+        out = self._loss_terms(g_outputs, g_gt, z_mean, z_logvar)
+        return self._add_normal(out, g_outputs, g_gt) if self.lambda_normal > 0 else out
+
+    def _loss_terms(self, g_outputs, g_gt, z_mean, z_logvar):
+        """loss_terms without the face-normal term: the reference's wired losses."""
         out = {}
         lat = self._latent_term(z_mean, z_logvar)
         reg = self._fc_regulariser()

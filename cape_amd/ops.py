@@ -2153,6 +2153,59 @@ class MaskedReconEdgeLossFn(torch.autograd.Function):
         return (dpred if unit else dpred * gtotal), None, None, None, None, None, None, None, None, None, None, ga, None, None
 
 
+class FaceNormalLossFn(torch.autograd.Function):
+    """total = [term_in +] w_normal * normal,  normal = mean over samples and faces of 1 - |n(pred + verts_ref) . n(gt + verts_ref)|
+    with n the unit face normal, zero for a degenerate face (lib/losses.py:27-52 on lib/utils.py:119-135; csrc/normal_loss/).
+    Returns (total, [normal]); only ``total`` is differentiable.  ``faces`` [F, 3] int32, ``fptr`` / ``fidx`` the
+    vertex -> incident-corner table (graph.vertex_face_table), all on the device.  ``term_in`` (a 0-dim tensor, e.g. the total
+    of the other loss terms; differentiable, its gradient is the incoming one unchanged) is added by the kernel that finishes
+    the loss.  The gradient w.r.t. ``pred`` is computed in forward (when ``pred`` requires one) and saved."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, verts_ref, faces, fptr, fidx, w_normal, term_in=None):
+        _lib.require_gpu()
+        gt = gt.contiguous()
+        N, M, _ = pred.shape
+        if pred.stride(2) != 1 or pred.stride(1) < 3 or (N > 1 and pred.stride(0) != M * pred.stride(1)):
+            pred = pred.contiguous()
+        ldp = int(pred.stride(1)) if M > 1 else 3
+        F = faces.shape[0]
+        assert pred.dtype == torch.float32 and gt.dtype == torch.float32 and gt.shape == (N, M, 3)
+        assert faces.dtype == torch.int32 and faces.is_contiguous() and fidx.numel() == 3 * F and fptr.numel() == M + 1
+        assert term_in is None or (term_in.dim() == 0 and term_in.dtype == torch.float32 and term_in.device == pred.device)
+        need = lib.cape_face_normal_loss_workspace_bytes(N, M, F)
+        ws = torch.empty((need + 3) // 4, device=pred.device, dtype=torch.float32)
+        out = torch.empty(1, device=pred.device, dtype=torch.float32)
+        total = torch.empty((), device=pred.device, dtype=torch.float32)
+        dpred = alloc_act(N, M, 3, pred.device, zero=False) if ctx.needs_input_grad[0] else None
+        ldd = int(dpred.stride(1)) if dpred is not None else 3
+        _log_launch("face_normal_loss", 0, N * (F * 120 + M * 12) + (N * (F * 12 + M * 200) if dpred is not None else 0),
+                    lambda: check(lib.cape_face_normal_loss_fwd_bwd(_ptr(pred), ldp, _ptr(gt), _ptr(verts_ref), _ptr(faces),
+                                                                    _ptr(fptr), _ptr(fidx), N, M, F, float(w_normal), _ptr(out),
+                                                                    _ptr(total), _ptr(term_in), _ptr(dpred), ldd, _ptr(ws),
+                                                                    need, _stream()),
+                                  "cape_face_normal_loss_fwd_bwd"))
+        ctx.set_materialize_grads(False)
+        if dpred is not None:
+            ctx.save_for_backward(dpred)
+        ctx.has_term = term_in is not None
+        ctx.mark_non_differentiable(out)
+        return total, out
+
+    @staticmethod
+    def backward(ctx, gtotal, _gout):
+        if gtotal is None:
+            return (None,) * 8
+        unit = UNIT_GRAD is not None and gtotal.data_ptr() == UNIT_GRAD.data_ptr()
+        gp = None
+        if ctx.needs_input_grad[0]:
+            (dpred,) = ctx.saved_tensors
+            gp = dpred if unit else dpred * gtotal
+        # d total / d term_in = 1: the incoming gradient itself, so that the op which produced term_in still recognises UNIT_GRAD
+        gt_in = gtotal if (ctx.has_term and ctx.needs_input_grad[7]) else None
+        return gp, None, None, None, None, None, None, gt_in
+
+
 class GanLossFn(torch.autograd.Function):
     """(lambda * gan_g, lambda * gan_d, [gan_g, gan_d]) from the discriminator's logits (lib/models.py:381-390,397):
     sigmoid cross entropy with smoothed labels, both means and both gradients in ONE launch (csrc/loss.hip gan_bce_kernel)

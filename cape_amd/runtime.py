@@ -74,7 +74,7 @@ class GraphedTrainStep(object):
         """The step's loss values stay where the loss kernels wrote them: under capture those tensors live in the graph's
         memory pool (kept alive by these references, so nothing later in the graph reuses them) and every replay rewrites
         them in place -- no copy launches."""
-        for k in ('loss_g', 'loss_d', 'recon', 'latent', 'edge'):
+        for k in ('loss_g', 'loss_d', 'recon', 'latent', 'edge', 'normal'):
             if k in out and torch.is_tensor(out[k]):
                 self.losses[k] = out[k].detach().reshape(())
 

@@ -51,6 +51,10 @@
  *   cape_masked_recon_edge_loss_fwd_bwd
  *                       lib/models.py:47-52, 357-369 loss_mask: the per-vertex weighted l1 / huber / l2 reconstruction
  *                       loss (TF Reduction.MEAN) + the edge loss, and their gradients w.r.t. the prediction.
+ *   cape_face_normal_loss_fwd_bwd
+ *                       lib/losses.py:27-52 face_normal_loss_calc on lib/utils.py:119-135 TriNormals / NormalizedNx3 (never
+ *                       called by the reference's lib/models.py: the "+ 0." slot of :393-395) and its gradient w.r.t. the
+ *                       prediction.
  *   cape_csr_validate   host-side structural check of an operator before upload.
  *   cape_smpl_dress / cape_smpl_joints / cape_smpl_skin
  *                       demos.py:155-161, 207-213 (de-normalise, clothing mask, + minimal body) and the SMPL forward pass
@@ -65,7 +69,7 @@
 extern "C" {
 #endif
 
-#define CAPE_ABI_VERSION 15
+#define CAPE_ABI_VERSION 16
 #define CAPE_MAX_SRC 8
 
 /* error codes (negative = argument error; positive values are hipError_t) */
@@ -623,6 +627,31 @@ int cape_masked_recon_edge_loss_fwd_bwd(const float *pred, int32_t ldp, const fl
                                         float inv_weight_sum, float w_recon, float w_edge, float *loss_out, float *total_out,
                                         const float *term_a, float w_a, const float *term_b, float *dpred, int32_t ldd,
                                         void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Face-normal loss (cape_amd/csrc/normal_loss/face_normal_loss.hip): the reference's face_normal_loss_calc
+ * (lib/losses.py:27-52) with lib/utils.py:119-135 TriNormals / NormalizedNx3, there a Python loop over the batch that its
+ * lib/models.py never calls.  With x = pred + verts_ref, y = gt + verts_ref (the shift of the edge loss, lib/models.py:374-375)
+ * and faces [F, 3] (int32, vertex indices in [0, M), any winding):
+ *   m(x) = (x[i1] - x[i0]) x (x[i2] - x[i0]);  n(x) = m / sqrt(ss + [ss == 0]), ss = m.m  (zero guard, no epsilon)
+ *   c = n(x).n(y);  loss_out[0] = normal = mean over all N*F faces of 1 - |c|
+ *   total_out (optional) = (term_in ? *term_in : 0) + w_normal * normal      term_in: optional device scalar
+ *   dpred (optional, [N, M, 3] with leading dimension ldd >= 3, pad columns not written) = w_normal * d normal / d pred:
+ *     per face g = -sign(c) (n(y) - c n(x)) / |m| / (N F), sign(0) = 0; corner k of the face receives g x (x[k+2] - x[k+1]).
+ *     A degenerate predicted or ground-truth face has n = 0: its term is 1 and it adds nothing to dpred.
+ * Unlike the reference (:38-46) no sample is dropped: with the template added no sample's normals are all zero.
+ * pred is read with leading dimension ldp >= 3 (pad never read), gt and verts_ref are dense.  vert_face_ptr [M + 1] /
+ * vert_face_idx [3 F]: per vertex its incident corners 3 * face + corner in a fixed order (cape_amd.graph.vertex_face_table);
+ * needed only with dpred.  dpred == NULL: value only (two launches), else three launches.  Fixed-order sums, no atomics.
+ * workspace: cape_face_normal_loss_workspace_bytes(N, M, F) bytes (CAPE_EINVAL for sizes < 1).
+ * CAPE_EINVAL for NULL operands, sizes < 1, ldp < 3, ldd < 3 or missing tables with dpred, a non-finite w_normal, term_in
+ * without total_out; CAPE_EWORKSPACE for a short workspace; all decided before any launch.
+ */
+int64_t cape_face_normal_loss_workspace_bytes(int32_t N, int32_t M, int32_t F);
+int cape_face_normal_loss_fwd_bwd(const float *pred, int32_t ldp, const float *gt, const float *verts_ref, const int32_t *faces,
+                                  const int32_t *vert_face_ptr, const int32_t *vert_face_idx, int32_t N, int32_t M, int32_t F,
+                                  float w_normal, float *loss_out, float *total_out, const float *term_in, float *dpred,
+                                  int32_t ldd, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
  * Adversarial losses on the discriminator's logits (lib/models.py:381-390, tf.nn.sigmoid_cross_entropy_with_logits with

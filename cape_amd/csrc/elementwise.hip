@@ -1498,7 +1498,9 @@ int spmm_multi_impl(const cape_spmm_term_t *terms, int32_t nterms, int32_t sum, 
     if (ag) {
         // the fused activation gradient: sum mode, vector form, the lanes of a row one aligned power-of-two group
         wide = wide && aligned8(ag->ax, ag->axs, ag->ldax, C, es);
-        if (!sum || !vec || !aligned4(ag->ax, ag->axs, ag->ldax, C, es) || !rm_fused(C / (wide ? 8 : 4)) || !ag->part) return CAPE_EINVAL;
+        // (at least 8 lanes per row: the block reduction of the bias sums starts at the 8-lane rotation)
+        if (!sum || !vec || !aligned4(ag->ax, ag->axs, ag->ldax, C, es) || !rm_fused(C / (wide ? 8 : 4)) || C / (wide ? 8 : 4) < 8 || !ag->part)
+            return CAPE_EINVAL;
         G = *ag;
     }
     const bool fused = vec && rm_fused(C / (wide ? 8 : 4));
@@ -1544,13 +1546,17 @@ static int actgrad_cq(const void *y, int64_t ys, int32_t ldy, const void *ax, in
 extern "C" int32_t cape_spmm_multi_actgrad_chunks(const float *y, int64_t y_sample_stride, int32_t ldy, const float *act_x,
                                                   int64_t act_x_sample_stride, int32_t ld_act_x, int32_t Mo, int32_t C) {
     if (!y || !act_x || Mo < 1 || C < 4 || (C & 3)) return CAPE_EINVAL;
-    return spmm_bps(Mo, actgrad_cq(y, y_sample_stride, ldy, act_x, act_x_sample_stride, ld_act_x, C));
+    const int cq = actgrad_cq(y, y_sample_stride, ldy, act_x, act_x_sample_stride, ld_act_x, C);
+    if (cq < 8) return CAPE_EINVAL;                           // see spmm_multi_impl
+    return spmm_bps(Mo, cq);
 }
 
 extern "C" int32_t cape_spmm_multi_actgrad_chunks_bf16(const void *y, int64_t y_sample_stride, int32_t ldy, const void *act_x,
                                                        int64_t act_x_sample_stride, int32_t ld_act_x, int32_t Mo, int32_t C) {
     if (!y || !act_x || Mo < 1 || C < 4 || (C & 3)) return CAPE_EINVAL;
-    return spmm_bps(Mo, actgrad_cq(y, y_sample_stride, ldy, act_x, act_x_sample_stride, ld_act_x, C, 2));
+    const int cq = actgrad_cq(y, y_sample_stride, ldy, act_x, act_x_sample_stride, ld_act_x, C, 2);
+    if (cq < 8) return CAPE_EINVAL;                           // see spmm_multi_impl
+    return spmm_bps(Mo, cq);
 }
 
 namespace {

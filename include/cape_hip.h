@@ -433,6 +433,9 @@ int cape_spmm_multi(const cape_spmm_term_t *terms, int32_t nterms, int32_t sum, 
  * and the bias-gradient partial sums of y over the rows of every block: bias_partials [N, chunks, 2, C] floats (term 0) in the
  * layout cape_bwd_prep_finalize reads with cape_bwd_prep_item_t.chunks = cape_spmm_multi_actgrad_chunks(...), R = 0.
  * That layer then needs no cape_bwd_prep launch.  act in {CAPE_ACT_LEAKY, CAPE_ACT_RELU}.
+ * Needs 16-byte aligned views whose rows split into a power-of-two number, 8 .. 64, of 4- or 8-channel work items (8 channels
+ * where every view allows it): C in 64 .. 512 in the 8-channel form, 32 .. 256 in the 4-channel form.  Anything else, fewer than
+ * 8 work items per row included, is CAPE_EINVAL from the launch and from the _chunks query alike; nothing is launched.
  */
 int32_t cape_spmm_multi_actgrad_chunks(const float *y, int64_t y_sample_stride, int32_t ldy, const float *act_x,
                                        int64_t act_x_sample_stride, int32_t ld_act_x, int32_t Mo, int32_t C);

@@ -196,6 +196,9 @@ SIGNATURES = {
     "cape_face_normal_loss_workspace_bytes": (_i64, [_i32, _i32, _i32]),
     "cape_face_normal_loss_fwd_bwd": (C.c_int, [_p, _i32, _p, _p, _p, _p, _p, _i32, _i32, _i32, _f32, _p, _p, _p, _p, _i32, _p,
                                                 _i64, _p]),
+    "cape_vertex_error": (C.c_int, [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _i32, _p]),
+    "cape_error_stats_workspace_bytes": (_i64, [_i32, _i32, _i32]),
+    "cape_error_stats": (C.c_int, [_p, _i32, _i32, C.POINTER(_i64), _i32, _p, _p, _p, _p, _p, _i64, _p]),
     "cape_smpl_dress": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
     "cape_smpl_joints": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cape_smpl_skin_tile": (C.c_int, [_i32, _i32]),

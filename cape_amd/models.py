@@ -1616,6 +1616,64 @@ class CAPE(base_model):
             string += '\ntime: {:.0f}s'.format(time.time() - t_start)
         return string, loss_recon, loss_latent, loss_edge
 
+    def test_errors(self, data, cond=None, cond2=None, labels=None, std=None, clothing_idx=None, quantiles=(0.5,),
+                    return_distances=False):
+        """The reference's test-set number (demos.py:63-85): the per-vertex Euclidean distance between reconstruction and
+        ``labels`` (default: ``data``), de-normalised by the training set's ``std`` ((V, 3), (3,), a scalar; default ones) and
+        restricted to ``clothing_idx`` (default every vertex, used in the order given), with its statistics -- all on the
+        device.  Batching, padding and seeding are predict's; per batch the generator, the losses and one distance
+        launch on the valid rows; at the end one statistics call, whose results come back in one small copy (the per-batch loss
+        scalars in another).  No prediction goes to the host and nothing synchronises inside the loop.
+        Returns a dict: recon / latent / edge (predict's averages, quirk C8), euclidean_mean, euclidean_std (population),
+        euclidean_median (when 0.5 is among ``quantiles``), quantiles {q: value} (numpy's linear rule, at most 4),
+        per_vertex_mean [Vc], per_sample_mean [size], count, nonfinite (> 0: mean, std and quantiles are NaN), and
+        distances [size, Vc] float32 when ``return_distances``."""
+        size = data.shape[0]
+        sd, idx, qs = ops.error_arguments(self.input_num_verts, self.nn_input_channel, size, std, clothing_idx, quantiles)
+        if labels is None:
+            labels = data
+        loss_recon, loss_latent, loss_edge = [], [], []
+        num_zero_phs = self.batch_size * (size / self.batch_size + 1) - size      # as predict (quirk C8)
+        self._get_session()
+        self._begin_pass()
+        sd_dev = torch.tensor(sd, dtype=torch.float32, device=self.device)
+        idx_dev = torch.tensor(idx, dtype=torch.int32, device=self.device)
+        dist = torch.empty((size, idx.size), dtype=torch.float32, device=self.device)
+        with torch.no_grad():
+            for begin in range(0, size, self.batch_size):
+                end = min(begin + self.batch_size, size)
+                bd = self._dev(self._pad(data, begin, end, data.shape[1:]))
+                bc = self._dev(self._pad(cond, begin, end, cond.shape[1:]))
+                bc2 = self._dev(self._pad(cond2, begin, end, cond2.shape[1:]))
+                y, y2 = self._conditions(bc, bc2)
+                x_hat, zm, zv = self.generator(bd, y, y2)
+                bl = self._dev(self._pad(labels, begin, end, labels.shape[1:]))
+                lt = self.loss_terms(x_hat, bl, zm, zv)
+                # the three scalars stay on the device until the end: no synchronisation inside the loop
+                loss_recon.append(lt['recon'])
+                loss_latent.append(lt['latent'])
+                loss_edge.append(lt['edge'])
+                xv = x_hat[:end - begin]
+                ops.vertex_error(xv if xv.dtype == torch.float32 else xv.float(), bl[:end - begin], sd_dev, idx_dev, dist,
+                                 row0=begin)
+            res = ops.error_statistics(dist, qs)
+            # float64 holds an fp32 scalar, an fp64 one and a Python float alike exactly: float() of it is predict's float(term)
+            scal = lambda t: (t if torch.is_tensor(t) else torch.tensor(float(t), dtype=torch.float64)).reshape(()).double().to(self.device)
+            losses = torch.stack([torch.stack([scal(t) for t in coll])
+                                  for coll in (loss_recon, loss_latent, loss_edge)]).cpu().numpy()
+
+        def calc_mean(coll):
+            coll = [float(v) for v in coll]
+            last = coll[-1]
+            total = np.sum(np.array(coll)[:-1]) * self.batch_size + last * (self.batch_size - num_zero_phs)
+            return total / size
+
+        res['recon'], res['latent'], res['edge'] = (calc_mean(c) for c in losses)
+        del res['order_ranks'], res['order_values'], res['euclidean_var']
+        if return_distances:
+            res['distances'] = dist.cpu().numpy()
+        return res
+
     def decode(self, data, cond=None, cond2=None):
         size = data.shape[0]
         self._get_session()

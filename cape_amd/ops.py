@@ -2659,3 +2659,138 @@ class VaeSampleKLFn(torch.autograd.Function):
                                          N, nz, _stream()), "cape_vae_sample_kl_bwd")
         dcond = gz[:, nz:] if (ctx.Cc and gz is not None) else None          # (a view: the condition's own gradient, no copy)
         return dmean, dlv, None, dcond
+
+
+# ---- evaluation: per-vertex Euclidean error and its statistics (csrc/eval/vertex_error.hip) -------------------------
+MAX_QUANTILES = 4            # 4 quantiles x (lo, hi) = the 8 ranks one cape_error_stats call takes
+
+
+def quantile_ranks(n, q):
+    """numpy's default (linear) quantile rule on n sorted values: pos = q (n - 1); returns (lo, hi, frac) with the quantile
+    a[lo] + (a[hi] - a[lo]) * frac.  Pure host arithmetic."""
+    n, q = int(n), float(q)
+    if n < 1 or not (0.0 <= q <= 1.0):
+        raise ValueError("quantile_ranks: n = %d, q = %r" % (n, q))
+    pos = q * (n - 1)
+    lo = int(np.floor(pos))
+    hi = int(np.ceil(pos))
+    return lo, hi, pos - lo
+
+
+def error_arguments(num_verts, channels, size, std=None, clothing_idx=None, quantiles=(0.5,)):
+    """The operands of an error evaluation checked and brought to the kernels' form, without a device: returns
+    (std [V, 3] float32, idx [Vc] int32, quantiles as a tuple of floats).  ``std`` None (ones), a scalar, (3,) or (V, 3);
+    ``clothing_idx`` None (every vertex) or unique integers in [0, V), kept in the order given."""
+    V = int(num_verts)
+    if int(channels) != 3:
+        raise ValueError("the Euclidean error needs 3 channels per vertex (nn_input_channel = %d)" % int(channels))
+    if std is None:
+        sd = np.ones((V, 3), dtype=np.float32)
+    else:
+        sd = np.asarray(std)
+        if sd.dtype.kind not in 'fiu' or sd.shape not in ((), (3,), (V, 3)):
+            raise ValueError("std: a scalar, (3,) or (%d, 3) array of numbers, not %s %s" % (V, sd.dtype, sd.shape))
+        sd = np.ascontiguousarray(np.broadcast_to(sd.astype(np.float64), (V, 3)))
+        if not np.isfinite(sd).all() or (sd < 0).any():
+            raise ValueError("std: values must be finite and >= 0")
+        sd = sd.astype(np.float32)
+        if not np.isfinite(sd).all():
+            raise ValueError("std: values must be finite in float32")
+    if clothing_idx is None:
+        idx = np.arange(V, dtype=np.int32)
+    else:
+        idx = np.asarray(clothing_idx)
+        if idx.dtype.kind not in 'iu' or idx.ndim != 1 or idx.size < 1:
+            raise ValueError("clothing_idx: a non-empty 1-d integer array, not %s %s" % (idx.dtype, idx.shape))
+        if int(idx.min()) < 0 or int(idx.max()) >= V:
+            raise ValueError("clothing_idx: values outside [0, %d)" % V)
+        if np.unique(idx).size != idx.size:
+            raise ValueError("clothing_idx: repeated vertices")
+        idx = np.ascontiguousarray(idx.astype(np.int32))
+    qs = tuple(float(q) for q in np.atleast_1d(np.asarray(quantiles, dtype=np.float64)))
+    if not 1 <= len(qs) <= MAX_QUANTILES:
+        raise ValueError("quantiles: 1 to %d per call, not %d" % (MAX_QUANTILES, len(qs)))
+    if any(not (0.0 <= q <= 1.0) for q in qs):
+        raise ValueError("quantiles: values outside [0, 1]")
+    if int(size) < 1 or int(size) * idx.size >= 2 ** 31:
+        raise ValueError("size * Vc = %d * %d: must be in [1, 2^31)" % (int(size), idx.size))
+    return sd, idx, qs
+
+
+def vertex_error(pred, gt, std, idx, dist, row0=0):
+    """dist[row0 + n, j] = || (pred[n, idx[j]] - gt[n, idx[j]]) * std[idx[j]] ||_2 for the N samples of ``pred`` (one launch).
+    ``pred`` [N, V, 3] fp32 (rows may be padded: a view of a wider buffer), ``gt`` [N, V, 3], ``std`` [V, 3], ``idx`` [Vc]
+    int32, ``dist`` [S, Vc] fp32 contiguous, all on the device.  Rows outside row0 .. row0 + N - 1 are not touched."""
+    _lib.require_gpu()
+    N, V, _ = pred.shape
+    if pred.stride(2) != 1 or pred.stride(1) < 3 or (N > 1 and pred.stride(0) != V * pred.stride(1)):
+        pred = pred.contiguous()
+    if V == 1:                                                   # one row per sample: its stride says nothing about the next sample's
+        pred = pred.contiguous()
+    ldp = int(pred.stride(1)) if V > 1 else 3
+    gt, std = gt.contiguous(), std.contiguous()
+    assert pred.dtype == torch.float32 and gt.dtype == torch.float32 and gt.shape == (N, V, 3) and pred.shape[2] == 3
+    assert std.dtype == torch.float32 and std.shape == (V, 3) and idx.dtype == torch.int32 and idx.is_contiguous()
+    assert dist.dtype == torch.float32 and dist.is_contiguous() and dist.dim() == 2 and dist.shape[1] == idx.numel()
+    S, Vc = dist.shape
+    _log_launch("vertex_error", 0, N * Vc * (4 + 36 + 4),
+                lambda: check(lib.cape_vertex_error(_ptr(pred), ldp, _ptr(gt), _ptr(std), _ptr(idx), N, V, Vc, _ptr(dist),
+                                                    int(row0), S, _stream()), "cape_vertex_error"))
+    return dist
+
+
+def error_stats_launch(dist, ranks):
+    """cape_error_stats on ``dist`` [S, Vc] for the sorted unique ``ranks`` (at most 8): the launches only, no copy, no
+    synchronisation.  Returns the fp64 device buffer [mean, var, nonfinite | per_vertex Vc | per_sample S | order (fp32) R]:
+    everything that goes to the host, in one piece."""
+    _lib.require_gpu()
+    assert dist.dtype == torch.float32 and dist.dim() == 2 and dist.is_contiguous() and dist.is_cuda
+    S, Vc = (int(d) for d in dist.shape)
+    R = len(ranks)
+    need = int(lib.cape_error_stats_workspace_bytes(S, Vc, R))
+    check(min(need, 0), "cape_error_stats_workspace_bytes")
+    ws = torch.empty((need + 7) // 8, device=dist.device, dtype=torch.float64)
+    out = torch.empty(3 + Vc + S + (R + 1) // 2, device=dist.device, dtype=torch.float64)
+    order = out[3 + Vc + S:].view(torch.float32)
+    arr = (C.c_int64 * max(R, 1))(*ranks)
+    passes = 6                                                   # row sums, variance, per-vertex, three digit passes
+    _log_launch("error_stats", 0, passes * S * Vc * 4,
+                lambda: check(lib.cape_error_stats(_ptr(dist), S, Vc, arr, R, _ptr(out), _ptr(order), _ptr(out, 2 * 3),
+                                                   _ptr(out, 2 * (3 + Vc)), _ptr(ws), need, _stream()), "cape_error_stats"))
+    return out
+
+
+def error_statistics(dist, quantiles=(0.5,)):
+    """Statistics of a finished distance buffer ``dist`` [S, Vc] (fp32, device, contiguous): one cape_error_stats call (12
+    launches) and one small copy to the host.  Returns a dict: count, nonfinite, euclidean_mean, euclidean_var,
+    euclidean_std (population, as np.std), quantiles {q: value} by numpy's linear rule (interpolated here in Python floats
+    from the two exact fp32 order statistics), euclidean_median when 0.5 is among them, per_vertex_mean [Vc] and
+    per_sample_mean [S] (float64), order_ranks / order_values (the exact order statistics the quantiles were made from).
+    With non-finite values in the buffer the mean, variance, std and quantiles are NaN."""
+    S, Vc = (int(d) for d in dist.shape)
+    qs = tuple(float(q) for q in quantiles)
+    if not 1 <= len(qs) <= MAX_QUANTILES:
+        raise ValueError("quantiles: 1 to %d per call, not %d" % (MAX_QUANTILES, len(qs)))
+    n = S * Vc
+    pos = [quantile_ranks(n, q) for q in qs]
+    ranks = sorted(set(r for lo, hi, _ in pos for r in (lo, hi)))
+    R = len(ranks)
+    host = error_stats_launch(dist, ranks).cpu()
+    vals = host[3 + Vc + S:].view(torch.float32).numpy()[:R].copy()
+    host = host.numpy()
+    nonfinite = int(host[2])
+    by_rank = dict(zip(ranks, (float(v) for v in vals)))
+    nan = float('nan')
+    qv = {}
+    for q, (lo, hi, frac) in zip(qs, pos):
+        a, b = by_rank[lo], by_rank[hi]
+        qv[q] = nan if nonfinite else a + (b - a) * frac
+    res = dict(count=n, nonfinite=nonfinite,
+               euclidean_mean=nan if nonfinite else float(host[0]),
+               euclidean_var=nan if nonfinite else float(host[1]),
+               euclidean_std=nan if nonfinite else float(np.sqrt(host[1])),
+               quantiles=qv, per_vertex_mean=host[3:3 + Vc].copy(), per_sample_mean=host[3 + Vc:3 + Vc + S].copy(),
+               order_ranks=list(ranks), order_values=vals)
+    if 0.5 in qv:
+        res['euclidean_median'] = qv[0.5]
+    return res

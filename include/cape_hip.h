@@ -59,6 +59,9 @@
  *   cape_smpl_dress / cape_smpl_joints / cape_smpl_skin
  *                       demos.py:155-161, 207-213 (de-normalise, clothing mask, + minimal body) and the SMPL forward pass
  *                       demos.py:267-283, 312-326 run through smplx (the model demos.py:22 creates), for a batch of meshes.
+ *   cape_vertex_error / cape_error_stats
+ *                       demos.py:68-78 the auto-encoding error: de-normalised per-vertex Euclidean distance on the clothing
+ *                       vertices and its mean / std / median (np.mean, np.std, np.median over all samples and vertices).
  */
 #ifndef CAPE_HIP_H
 #define CAPE_HIP_H
@@ -887,6 +890,35 @@ int cape_smpl_skin_tile(int32_t K, int32_t J);
 int cape_smpl_skin(const float *T, int64_t T_sample_stride, const float *basis, int32_t K, const float *coef, const float *G,
                    const int32_t *ell_joint, const float *ell_weight, int32_t ell_width, const float *transl, int32_t J,
                    int32_t V, int32_t N, float *out, int64_t out_sample_stride, void *stream);
+
+/*
+ * Per-vertex Euclidean error and its statistics (cape_amd/csrc/eval/vertex_error.hip): the auto-encoding error of
+ * demos.py:68-78, there numpy on predictions copied to the host.  pred / gt [N, V, 3] in normalised units (pred with leading
+ * dimension ldp >= 3, pad never read; gt dense), std_ [V, 3] the training set's, idx [Vc] vertex indices in [0, V), in the
+ * order the columns of dist take:
+ *   dist[row0 + n, j] = sqrt( sum_c ((pred[n, idx[j], c] - gt[n, idx[j], c]) * std_[idx[j], c])^2 )      n < N
+ * (the mean the reference adds to both sides cancels).  dist [S, Vc] fp32 dense lives for the whole evaluation; a call
+ * writes rows row0 .. row0 + N - 1 and nothing else.  Differences and products in fp32, the sum of squares and the root in
+ * fp64, rounded once.  An index outside [0, V) reads nothing and yields NaN.  One launch.
+ *
+ * cape_error_stats reduces a finished dist [S, Vc] (n = S * Vc values, 4-byte aligned; 16-byte aligned takes vector loads):
+ *   out_moments [3] fp64   mean, population variance (two passes: sum (d - mean)^2 / n), number of non-finite values
+ *   out_order   [R] fp32   the ranks[r]-th smallest value (0-based), exact: radix select on the bit patterns as unsigned
+ *                          integers (their order for values >= +0; NaN patterns sort last), digit passes of 11 / 11 / 10 bits
+ *   per_vertex  [Vc] fp64  mean over the samples;  per_sample [S] fp64  mean over the vertices
+ * ranks: HOST array of R <= 8 ranks, passed by value in the launch.  All outputs and the workspace are device memory; the
+ * workspace (8-byte aligned) needs no initialisation.  12 launches; every sum has a fixed order (fp64, block partials,
+ * the last reduction in a launch of its own); the histograms cross workgroups as integer device-scope adds, read by the next
+ * launch.  Same bits run after run: grids depend on the sizes only.
+ * CAPE_EINVAL for NULL operands, N, V, Vc, S < 1, Vc > V, ldp < 3, row0 < 0 or row0 + N > S, S * Vc >= 2^31, R outside 1..8,
+ * a rank outside [0, S * Vc), a misaligned buffer; CAPE_EWORKSPACE for a short workspace; all decided before any launch.
+ */
+int cape_vertex_error(const float *pred, int32_t ldp, const float *gt, const float *std_, const int32_t *idx, int32_t N,
+                      int32_t V, int32_t Vc, float *dist, int32_t row0, int32_t S, void *stream);
+int64_t cape_error_stats_workspace_bytes(int32_t S, int32_t Vc, int32_t R);
+int cape_error_stats(const float *dist, int32_t S, int32_t Vc, const int64_t *ranks, int32_t R, double *out_moments,
+                     float *out_order, double *per_vertex, double *per_sample, void *workspace, int64_t workspace_bytes,
+                     void *stream);
 
 #ifdef __cplusplus
 }

@@ -203,6 +203,15 @@ SIGNATURES = {
     "cape_smpl_joints": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _p, _p, _p]),
     "cape_smpl_skin_tile": (C.c_int, [_i32, _i32]),
     "cape_smpl_skin": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p]),
+    "cape_smpl_skin_bwd_plan": (C.c_int, [_i32, _i32, _i32, _i32, _p]),
+    "cape_smpl_skin_bwd_workspace_bytes": (C.c_int64, [_i32, _i32, _i32, _i32]),
+    "cape_smpl_skin_bwd": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _p, _p, _i32, _p, _i64, _i32, _i32, _i32, _i32, _p, _i64, _p,
+                                     _i64, _p]),
+    "cape_smpl_joints_bwd": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _i32, _i32, _p, _p, _i32, _i32, _p, _p,
+                                       _p, _p, _p]),
+    "cape_smpl_jreg_bwd": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _i64, _p]),
+    "cape_smpl_dress_bwd": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _p]),
+    "cape_smpl_weighted_l2": (C.c_int, [_p, _i64, _p, _i64, _p, _f32, _i32, _i32, _p, _p, _i64, _p]),
 }
 
 # bf16-storage variants with the argument list of their fp32 namesake (include/cape_hip.h, last section)

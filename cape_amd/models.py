@@ -1740,3 +1740,138 @@ class CAPE(base_model):
                 posed.append(vo.cpu().numpy())
                 clothed.append(T.cpu().numpy())
         return np.concatenate(posed, 0), np.concatenate(clothed, 0)
+
+    def fit_posed(self, target, pose, cond, cond2, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None, z0=None,
+                  weights=None, steps=200, lr=0.1, lambda_z=0.0, lambda_edge=0.0, optimize_pose=False, optimize_transl=False):
+        """The latent codes that explain posed meshes: gradient descent (Adam) on ``z`` through
+        decoder -> cape_smpl_dress -> SMPL posing, all on the device (``smpl.dress_diff`` / ``SMPL.forward_diff``).
+
+        ``target`` [size, V, 3] posed meshes in SMPL topology; ``pose`` / ``transl`` / ``body_model`` / ``mean`` / ``std`` /
+        ``clothing_idx`` / ``minimal_shape`` as in ``decode_posed``; ``cond`` / ``cond2`` condition EMBEDDINGS, one row for all
+        samples or one per sample (decode_posed's rule); ``z0`` [size, nz] the starting codes (zeros); ``weights`` [V]
+        per-vertex weights of the data term (ones).  Per sample the objective is
+
+            sum_v w_v |posed_v - target_v|^2 / sum_v w_v  +  lambda_z mean(z^2)  [+ lambda_edge edge(posed, target)]
+
+        (edge: the training loss's edge term between the posed mesh and the target, per sample; asking for it costs one
+        element-wise product and one sum on [N, V, 3] per step in torch, where the two gradients meet).  The leaves are ``z``, and
+        ``pose`` / ``transl`` with ``optimize_pose`` / ``optimize_transl`` (``transl`` then starts at zero when None); the
+        samples are independent.  The model's variables take no gradient and no weight-gradient kernel runs; optimiser state
+        and gradient buckets stay as a ``decode`` call leaves them.  The defaults (200 steps, lr 0.1, lambda_z 0) come from
+        the synthetic recovery run of DESIGN 7f; the data term is in squared metres (about 1e-6 for a code one standard
+        deviation off), so a useful ``lambda_z`` is of that order or below.  The rows of ``loss`` before the last come from
+        the differentiated forward, whose decoder kernels differ from ``decode``'s in the last bit; the last row, ``posed``
+        and ``clothed`` are evaluated exactly as ``decode_posed`` evaluates the returned leaves.
+
+        Returns a dict: ``z`` [size, nz], ``pose`` [size, 3J], ``transl`` [size, 3] or None, ``posed`` / ``clothed``
+        [size, V, 3] for the returned leaves, ``loss`` [steps + 1, size] the data term per sample (row 0: before the first
+        update)."""
+        import ctypes as C
+        from . import smpl as smpl_mod
+        body = getattr(body_model, 'model', body_model)
+        target = np.asarray(target, dtype=np.float32)
+        size, V, J, bs, nz = target.shape[0], body.V, body.J, self.batch_size, int(self.nz)
+        if target.shape != (size, V, 3):
+            raise ValueError("target: [size, %d, 3] expected, got %s" % (V, target.shape))
+        pose = np.asarray(pose, dtype=np.float32).reshape(-1, 3 * J)
+        if pose.shape[0] not in (1, size):
+            raise ValueError("pose: %d rows for %d samples" % (pose.shape[0], size))
+        if transl is None and optimize_transl:
+            transl = np.zeros((size, 3), np.float32)
+        if transl is not None:
+            transl = np.asarray(transl, dtype=np.float32).reshape(-1, 3)
+            if transl.shape[0] not in (1, size):
+                raise ValueError("transl: %d rows for %d samples" % (transl.shape[0], size))
+        cond, cond2 = np.asarray(cond, dtype=np.float32), np.asarray(cond2, dtype=np.float32)
+        if cond.shape[0] not in (1, size) or cond2.shape[0] != cond.shape[0]:
+            raise ValueError("cond / cond2: one row, or one per sample")
+        z0 = np.zeros((size, nz), np.float32) if z0 is None else np.asarray(z0, dtype=np.float32)
+        if z0.shape != (size, nz):
+            raise ValueError("z0: [%d, %d] expected" % (size, nz))
+        w = np.ones(V, np.float32) if weights is None else np.asarray(weights, dtype=np.float32).reshape(-1)
+        if w.shape != (V,) or not float(w.sum()) > 0.0:
+            raise ValueError("weights: [%d] with a positive sum expected" % V)
+        steps = int(steps)
+        inv_wsum = 1.0 / float(w.astype(np.float64).sum())
+        rows = lambda a, b, e: np.repeat(a, e - b, 0) if a.shape[0] == 1 else a[b:e]
+
+        def padded(a, b, e):            # rows b..e of a (one row: repeated) in a zero block of batch_size rows
+            out = np.zeros((bs,) + a.shape[1:], np.float32)
+            out[:e - b] = rows(a, b, e)
+            return self._dev(out)
+
+        dressing = smpl_mod._DressArrays(mean, std, clothing_idx, self.verts_ref if minimal_shape is None else minimal_shape,
+                                         V, self.device)
+        w_dev = self._dev(w)
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        self._get_session()
+        self._begin_pass()
+        if lambda_edge:
+            _, ed, vptr, vidx = self._edge_tables()
+            no_ref = torch.zeros((V, 3), dtype=torch.float32, device=self.device)
+        res = dict(z=[], pose=[], transl=[], posed=[], clothed=[], loss=[])
+        stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        # the model's variables are constants here: no gradient bucket to write into and, while the steps run, nothing that
+        # requires a gradient (the ops then skip their weight-gradient kernels)
+        grad_views, self._grad_views = self._grad_views, {}
+        trainable = [v for v in self._vars.values() if v.requires_grad]
+
+        def freeze(on):
+            for v in trainable:
+                v.requires_grad_(not on)
+
+        try:
+            for begin in range(0, size, bs):
+                end = min(begin + bs, size)
+                nb = end - begin
+                z = padded(z0, begin, end).requires_grad_(True)
+                bc = padded(cond, begin, end) if cond.shape[0] > 1 else self._dev(np.repeat(cond, bs, 0))
+                bc2 = padded(cond2, begin, end) if cond2.shape[0] > 1 else self._dev(np.repeat(cond2, bs, 0))
+                bp = padded(pose, begin, end).requires_grad_(bool(optimize_pose))
+                bt = None if transl is None else padded(transl, begin, end).requires_grad_(bool(optimize_transl))
+                tgt = padded(target, begin, end)
+                leaves = [z] + ([bp] if optimize_pose else []) + ([bt] if optimize_transl else [])
+                opt = torch.optim.Adam(leaves, lr=float(lr))
+                loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
+                grad = torch.zeros((bs, V, 3), dtype=torch.float32, device=self.device)       # padded rows stay zero
+
+                def evaluate(step, want_grad):
+                    with self.variable_scope('generator'):
+                        x = self.decoder_cond_vert(torch.cat([z, bc, bc2], 1), bc, bc2, use_res_block=self.use_res_block_dec)
+                    T = dressing.diff(x.float().contiguous())
+                    posed, _ = body.forward_diff(T, bp, None, bt)
+                    _lib.check(_lib.lib.cape_smpl_weighted_l2(ptr(posed), 3 * V, ptr(tgt), 3 * V, ptr(w_dev), inv_wsum, nb, V,
+                                                              ptr(loss[step]), ptr(grad) if want_grad else None, 3 * V, stream()),
+                               "cape_smpl_weighted_l2")
+                    return T, posed
+
+                freeze(True)
+                try:
+                    for step in range(steps):
+                        T, posed = evaluate(step, True)
+                        opt.zero_grad(set_to_none=True)
+                        if lambda_edge:
+                            # the batch mean of the training loss's edge term, scaled back to a sum over the samples
+                            e_total, _ = ops.ReconEdgeLossFn.apply(posed[:nb], tgt[:nb], no_ref, ed, vptr, vidx, 0.0,
+                                                                   float(lambda_edge) * nb)
+                            torch.autograd.backward([posed, e_total], [grad, None])
+                        else:
+                            torch.autograd.backward([posed], [grad])
+                        if lambda_z:
+                            z.grad.add_(z.detach(), alpha=2.0 * float(lambda_z) / nz)
+                        opt.step()
+                finally:
+                    freeze(False)
+                with torch.no_grad():            # the returned leaves as decode_posed evaluates them, kernel for kernel
+                    T, posed = evaluate(steps, False)
+                res['z'].append(z.detach()[:nb].cpu().numpy())
+                res['pose'].append(bp.detach()[:nb].cpu().numpy())
+                res['transl'].append(None if bt is None else bt.detach()[:nb].cpu().numpy())
+                res['posed'].append(posed[:nb].cpu().numpy())
+                res['clothed'].append(T[:nb].cpu().numpy())
+                res['loss'].append(loss[:, :nb].cpu().numpy())
+        finally:
+            self._grad_views = grad_views
+        cat = lambda k, ax=0: np.concatenate(res[k], ax)
+        return dict(z=cat('z'), pose=cat('pose'), transl=None if transl is None else cat('transl'), posed=cat('posed'),
+                    clothed=cat('clothed'), loss=cat('loss', 1))

@@ -3,13 +3,18 @@ bodies (reference demos.py:155-161, 207-213 and :249-331, which go through ``smp
 
   load_smpl_model(path)      an SMPL model file (.npz, or a chumpy-free .pkl) -> ``SMPL`` with its arrays on the device
   SMPL.forward(...)          batched forward pass on torch device tensors (libcape_hip.so cape_smpl_joints / cape_smpl_skin)
+  SMPL.forward_diff(...)     the same as an autograd function: gradients to the rest body, pose, betas and translation
+                             (cape_smpl_skin_bwd / cape_smpl_joints_bwd / cape_smpl_jreg_bwd)
   SMPL.pose(...)             the same on numpy arrays
   dress(...)                 de-normalise + clothing mask + minimal body (cape_smpl_dress)
+  dress_diff(...)            the same with a gradient to the displacements (cape_smpl_dress_bwd)
   create(...), body_models   an ``smplx``-compatible factory: with a one-line ``smplx.py`` in the reference checkout
                              (``from cape_amd.smpl import body_models``) demos.py poses through the device unchanged
 
 The joints are regressed from the rest body the caller passes -- in demos.py the CLOTHED body, because it overwrites the
-model's ``v_template`` with it.  There is no CPU fallback and no gradient: inputs that require grad are refused.
+model's ``v_template`` with it.  There is no CPU fallback.  ``forward`` and ``dress`` carry no gradient (``forward`` refuses
+inputs that require one); ``forward_diff`` and ``dress_diff`` are the differentiable forms, hand-derived backward kernels
+behind ``torch.autograd.Function``s that save their inputs only.
 """
 import ctypes as C
 import os
@@ -123,9 +128,16 @@ class SMPL(object):
         # [shapedirs | posedirs] planar [K][3][V]: lanes of a wave load consecutive words of one coefficient's plane
         basis = np.concatenate([m["shapedirs"].transpose(2, 1, 0), m["posedirs"].transpose(2, 1, 0)], 0)
         jsd = np.einsum("jv,vcb->bjc", jreg.toarray(), m["shapedirs"])          # J_regressor . shapedirs, [B][J][3]
+        # the regressor's transpose for the backward's gather per vertex: CSC of [J, V] = CSR of [V, J]
+        jt = jreg.T.tocsr()
+        jt.sort_indices()
+        tp, ti = jt.indptr.astype(np.int32), jt.indices.astype(np.int32)
+        _lib.check(_lib.lib.cape_csr_validate(V, J, int(jt.nnz), tp.ctypes.data_as(C.c_void_p),
+                                              ti.ctypes.data_as(C.c_void_p)), "SMPL J_regressor (transposed)")
         self.layouts = dict(rowptr=(rp, np.int32), colidx=(ci, np.int32), vals=(jreg.data, np.float32),
                             ell_j=(ell_j, np.int32), ell_w=(ell_w, np.float32), basis=(basis, np.float32),
-                            jshapedirs=(jsd, np.float32), v_template=(m["v_template"], np.float32))
+                            jshapedirs=(jsd, np.float32), v_template=(m["v_template"], np.float32),
+                            jt_colptr=(tp, np.int32), jt_rowidx=(ti, np.int32), jt_vals=(jt.data, np.float32))
         self._dev = None
         self._parents_c = (C.c_int32 * J)(*[int(x) for x in self.parents])
 
@@ -146,11 +158,8 @@ class SMPL(object):
     def basis_bytes(self):
         return self.layouts["basis"][0].size * 4
 
-    def forward(self, verts, pose, betas=None, transl=None, out=None):
-        """Pose N meshes.  ``verts`` [N,V,3] or [1,V,3] (one rest body for every pose; None: the template), ``pose`` [N,J*3]
-        axis-angle (joint 0 = global orientation), ``betas`` [N,<=B], ``transl`` [N,3]: float32 tensors on this model's device.
-        Returns (vertices [N,V,3], joints [N,J,3]); with ``out`` = that pair preallocated, nothing synchronises the host, so
-        the call can be captured in a graph."""
+    def _arguments(self, verts, pose, betas, transl, grad):
+        """forward's argument checks; ``betas`` comes back padded to the model's shape rows (or None)."""
         J, V, d = self.J, self.V, self._upload()
         if verts is None:
             verts = d.v_template[None]
@@ -159,7 +168,7 @@ class SMPL(object):
         for name, t in (("verts", verts), ("pose", pose), ("betas", betas), ("transl", transl)):
             if t is None:
                 continue
-            if t.requires_grad:
+            if t.requires_grad and not grad:
                 raise RuntimeError("cape_amd.smpl: forward only, %s requires grad" % name)
             if t.dtype != torch.float32 or t.device != d.device or not t.is_contiguous():
                 raise ValueError("cape_amd.smpl: %s must be a contiguous float32 tensor on %s" % (name, d.device))
@@ -167,7 +176,6 @@ class SMPL(object):
             raise ValueError("pose: %d values per sample, the model has %d joints" % (pose.shape[1], J))
         if verts.dim() != 3 or verts.shape[1:] != (V, 3) or verts.shape[0] not in (1, N):
             raise ValueError("verts: [%d or 1, %d, 3] expected, got %s" % (N, V, tuple(verts.shape)))
-        B = 0
         if betas is not None:
             betas = betas.reshape(N, -1)
             B = betas.shape[1]
@@ -177,28 +185,93 @@ class SMPL(object):
                 betas = None
             elif B < self.num_betas:      # the basis keeps the model's shape rows in front of the pose rows: pad with zeros
                 betas = torch.cat([betas, betas.new_zeros((N, self.num_betas - B))], 1)
-                B = self.num_betas
         if transl is not None and tuple(transl.shape) not in ((N, 3),):
             raise ValueError("transl: [%d, 3] expected" % N)
+        return verts, pose, betas, transl
+
+    def _basis(self, B):
+        """The blend basis for B shape rows: with no betas it starts past the model's shape rows."""
+        return C.c_void_p(self._dev.basis.data_ptr() + 4 * 3 * self.V * (self.num_betas - B))
+
+    def _joints(self, verts, pose, betas, transl, jo):
+        """cape_smpl_joints on checked arguments: (coef, G), the posed joints into ``jo`` (None: not wanted)."""
+        J, V, d, N = self.J, self.V, self._dev, pose.shape[0]
+        B = 0 if betas is None else betas.shape[1]
+        coef = torch.empty((N, B + 9 * (J - 1)), dtype=torch.float32, device=d.device)
+        G = torch.empty((N, J, 12), dtype=torch.float32, device=d.device)
+        _lib.check(_lib.lib.cape_smpl_joints(_p(verts), 0 if verts.shape[0] == 1 else 3 * V, _p(d.rowptr), _p(d.colidx),
+                                             _p(d.vals), _p(pose), _p(betas), B, _p(d.jshapedirs), _p(transl),
+                                             self._parents_c, J, V, N, _p(coef), _p(G), _p(jo), _stream()), "cape_smpl_joints")
+        return coef, G
+
+    def _launch(self, verts, pose, betas, transl, out):
+        J, V, d, N = self.J, self.V, self._dev, pose.shape[0]
         if out is None:
             out = (torch.empty((N, V, 3), dtype=torch.float32, device=d.device),
                    torch.empty((N, J, 3), dtype=torch.float32, device=d.device))
         vo, jo = out
         if tuple(vo.shape) != (N, V, 3) or tuple(jo.shape) != (N, J, 3) or not (vo.is_contiguous() and jo.is_contiguous()):
             raise ValueError("out: contiguous [N,V,3] and [N,J,3] float32 tensors expected")
-        K = B + 9 * (J - 1)
-        coef = torch.empty((N, K), dtype=torch.float32, device=d.device)
-        G = torch.empty((N, J, 12), dtype=torch.float32, device=d.device)
-        tss = 0 if verts.shape[0] == 1 else 3 * V
-        s = _stream()
-        _lib.check(_lib.lib.cape_smpl_joints(_p(verts), tss, _p(d.rowptr), _p(d.colidx), _p(d.vals), _p(pose),
-                                             _p(betas), B, _p(d.jshapedirs), _p(transl), self._parents_c, J, V, N,
-                                             _p(coef), _p(G), _p(jo), s), "cape_smpl_joints")
-        # no betas: the basis starts past the model's shape rows
-        basis = C.c_void_p(d.basis.data_ptr() + 4 * 3 * V * (self.num_betas - B))
-        _lib.check(_lib.lib.cape_smpl_skin(_p(verts), tss, basis, K, _p(coef), _p(G), _p(d.ell_j), _p(d.ell_w),
-                                           self.ell_width, _p(transl), J, V, N, _p(vo), 3 * V, s), "cape_smpl_skin")
+        coef, G = self._joints(verts, pose, betas, transl, jo)
+        _lib.check(_lib.lib.cape_smpl_skin(_p(verts), 0 if verts.shape[0] == 1 else 3 * V, self._basis(coef.shape[1] - 9 * (J - 1)),
+                                           coef.shape[1], _p(coef), _p(G), _p(d.ell_j), _p(d.ell_w), self.ell_width, _p(transl),
+                                           J, V, N, _p(vo), 3 * V, _stream()), "cape_smpl_skin")
         return vo, jo
+
+    def forward(self, verts, pose, betas=None, transl=None, out=None):
+        """Pose N meshes.  ``verts`` [N,V,3] or [1,V,3] (one rest body for every pose; None: the template), ``pose`` [N,J*3]
+        axis-angle (joint 0 = global orientation), ``betas`` [N,<=B], ``transl`` [N,3]: float32 tensors on this model's device.
+        Returns (vertices [N,V,3], joints [N,J,3]); with ``out`` = that pair preallocated, nothing synchronises the host, so
+        the call can be captured in a graph.  No gradient: see ``forward_diff``."""
+        return self._launch(*self._arguments(verts, pose, betas, transl, grad=False), out=out)
+
+    def forward_diff(self, verts, pose, betas=None, transl=None):
+        """``forward`` (same arguments, same checks, bitwise the same values) as an autograd function: gradients on the returned
+        vertices and / or joints flow to whichever of ``verts`` ([1,V,3]: summed over the samples), ``pose``, ``betas`` and
+        ``transl`` require them.  The inputs are all that is saved; backward recomputes the joint transforms."""
+        verts, pose, betas, transl = self._arguments(verts, pose, betas, transl, grad=True)
+        return _PoseFn.apply(self, verts, pose, betas, transl)
+
+    def _backward(self, verts, pose, betas, transl, gV, gJ, need):
+        """(dT, dpose, dbetas, dtransl) for the wanted ones of ``need`` (four flags), None for the others."""
+        J, V, d, N = self.J, self.V, self._dev, pose.shape[0]
+        lib, s = _lib.lib, _stream()
+        need_T, need_pose, need_betas, need_transl = need
+        need_betas = need_betas and betas is not None
+        need_transl = need_transl and transl is not None
+        if (gV is None and gJ is None) or not (need_T or need_pose or need_betas or need_transl):
+            return None, None, None, None
+        B = 0 if betas is None else betas.shape[1]
+        K = B + 9 * (J - 1)
+        tss = 0 if verts.shape[0] == 1 else 3 * V
+        new = lambda *shape: torch.empty(shape, dtype=torch.float32, device=d.device)
+        ws, blocks, q, need_coef = None, 0, None, bool(need_pose or need_betas)
+        if gV is not None:
+            gV = gV.contiguous()
+            coef, G = self._joints(verts, pose, betas, transl, None)
+            plan = (C.c_int32 * 3)()
+            _lib.check(lib.cape_smpl_skin_bwd_plan(K, J, V, N, plan), "cape_smpl_skin_bwd_plan")
+            blocks = int(plan[1])
+            ws = new(N * blocks * int(plan[2]))
+            q = new(N, V, 3) if need_T else None
+            _lib.check(lib.cape_smpl_skin_bwd(_p(verts), tss, self._basis(B), K, _p(coef), _p(G), _p(d.ell_j), _p(d.ell_w),
+                                              self.ell_width, _p(gV), 3 * V, J, V, N, int(need_coef), _p(q), 3 * V, _p(ws),
+                                              4 * ws.numel(), s), "cape_smpl_skin_bwd")
+        if gJ is not None:
+            gJ = gJ.contiguous()
+        dpose = new(N, 3 * J) if need_pose else None
+        dbetas = new(N, B) if need_betas else None
+        dtransl = new(N, 3) if need_transl else None
+        dJn = new(N, J, 3) if need_T else None
+        _lib.check(lib.cape_smpl_joints_bwd(_p(verts), tss, _p(d.rowptr), _p(d.colidx), _p(d.vals), _p(pose), _p(betas), B,
+                                            _p(d.jshapedirs), self._parents_c, J, V, N, _p(gJ), _p(ws), blocks, int(need_coef),
+                                            _p(dpose), _p(dbetas), _p(dtransl), _p(dJn), s), "cape_smpl_joints_bwd")
+        dT = None
+        if need_T:
+            dT = new(verts.shape[0], V, 3)
+            _lib.check(lib.cape_smpl_jreg_bwd(_p(q), 3 * V, _p(d.jt_colptr), _p(d.jt_rowidx), _p(d.jt_vals), _p(dJn), J, V, N,
+                                              int(verts.shape[0] == 1), _p(dT), 3 * V, s), "cape_smpl_jreg_bwd")
+        return dT, dpose, dbetas, dtransl
 
     __call__ = forward
 
@@ -210,6 +283,47 @@ class SMPL(object):
             verts = None if verts is None else np.asarray(verts).reshape(-1, self.V, 3)
             vo, jo = self.forward(t(verts), t(pose), t(betas), t(transl))
             return vo.cpu().numpy(), jo.cpu().numpy()
+
+
+class _PoseFn(torch.autograd.Function):
+    """SMPL.forward_diff: the forward entries, and in backward the kernels of csrc/smpl/smpl_bwd.hip on the saved inputs."""
+
+    @staticmethod
+    def forward(ctx, model, verts, pose, betas, transl):
+        vo, jo = model._launch(verts.detach(), pose.detach(), None if betas is None else betas.detach(),
+                               None if transl is None else transl.detach(), None)
+        ctx.model = model
+        ctx.has = (betas is not None, transl is not None)
+        ctx.save_for_backward(*[t for t in (verts, pose, betas, transl) if t is not None])
+        ctx.set_materialize_grads(False)
+        return vo, jo
+
+    @staticmethod
+    def backward(ctx, gV, gJ):
+        saved = list(ctx.saved_tensors)
+        verts, pose = saved[0], saved[1]
+        betas = saved[2] if ctx.has[0] else None
+        transl = saved[-1] if ctx.has[1] else None
+        with torch.no_grad():
+            return (None,) + ctx.model._backward(verts, pose, betas, transl, gV, gJ, ctx.needs_input_grad[1:5])
+
+
+class _DressFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, arrays, disp):
+        ctx.arrays = arrays
+        ctx.set_materialize_grads(False)
+        return arrays(disp.detach())
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None or not ctx.needs_input_grad[1]:
+            return None, None
+        a, g = ctx.arrays, g.contiguous()
+        out = torch.empty_like(g)
+        _lib.check(_lib.lib.cape_smpl_dress_bwd(_p(g), 3 * a.V, _p(a.std), _p(a.mask), _p(out), 3 * a.V, g.shape[0], a.V,
+                                                _stream()), "cape_smpl_dress_bwd")
+        return None, out
 
 
 # ---- dress ---------------------------------------------------------------------------------------------------------------
@@ -234,11 +348,22 @@ class _DressArrays(object):
                                             _p(out), 3 * V, N, V, _stream()), "cape_smpl_dress")
         return out
 
+    def diff(self, disp):
+        """The same with a gradient to ``disp``: mask * std * the incoming gradient (cape_smpl_dress_bwd)."""
+        if disp.dtype != torch.float32 or not disp.is_contiguous() or tuple(disp.shape[1:]) != (self.V, 3):
+            raise ValueError("disp: contiguous float32 [N, %d, 3] expected" % self.V)
+        return _DressFn.apply(self, disp)
+
 
 def dress(disp, mean, std, clothing_idx, minimal_shape):
     """demos.py:155-161: ``minimal_shape + mask(clothing_idx) * (disp * std + mean)`` for a device tensor ``disp`` [N,V,3];
     the other arguments are host arrays.  Returns the clothed rest bodies [N,V,3] on the device."""
     return _DressArrays(mean, std, clothing_idx, minimal_shape, disp.shape[1], disp.device)(disp)
+
+
+def dress_diff(disp, mean, std, clothing_idx, minimal_shape):
+    """``dress`` with a gradient to ``disp``."""
+    return _DressArrays(mean, std, clothing_idx, minimal_shape, disp.shape[1], disp.device).diff(disp)
 
 
 # ---- smplx-compatible factory (demos.py:22-24, 267-283, 312-326) -------------------------------------------------------------

@@ -56,7 +56,7 @@
  *                       called by the reference's lib/models.py: the "+ 0." slot of :393-395) and its gradient w.r.t. the
  *                       prediction.
  *   cape_csr_validate   host-side structural check of an operator before upload.
- *   cape_smpl_dress / cape_smpl_joints / cape_smpl_skin
+ *   cape_smpl_dress / cape_smpl_joints / cape_smpl_skin (and their backward, cape_smpl_*_bwd)
  *                       demos.py:155-161, 207-213 (de-normalise, clothing mask, + minimal body) and the SMPL forward pass
  *                       demos.py:267-283, 312-326 run through smplx (the model demos.py:22 creates), for a batch of meshes.
  *   cape_vertex_error / cape_error_stats
@@ -856,9 +856,9 @@ int cape_cheb_fused_debug_timestamps(void *ts);
 /*
  * SMPL posing (cape_amd/csrc/smpl/smpl.hip) -- the last step of demos.py (:155-161, 207-213 and :267-283, 312-326: the
  * decoder output de-normalised, masked to the clothing vertices, added to the minimal body, then posed by the SMPL forward
- * pass of smplx, one mesh per call on the CPU), for N meshes at once.  Forward only.  Model arrays in the device layouts
- * cape_amd.smpl builds at load (SMPL file layouts: v_template [V,3], J_regressor [J,V], weights [V,J],
- * posedirs [V,3,9(J-1)], shapedirs [V,3,B]):
+ * pass of smplx, one mesh per call on the CPU), for N meshes at once.  The forward entries first, their backward below.
+ * Model arrays in the device layouts cape_amd.smpl builds at load (SMPL file layouts: v_template [V,3],
+ * J_regressor [J,V], weights [V,J], posedirs [V,3,9(J-1)], shapedirs [V,3,B]):
  *   jreg rowptr / colidx / vals   J_regressor as CSR (J rows, columns < V, checked at load)
  *   jshapedirs [B][J][3]          J_regressor . shapedirs, so that joints need no pass over the shape basis
  *   basis      [K][3][V]          planar [shapedirs[:, :, :B] | posedirs] coefficient-major, K = B + 9(J-1)
@@ -890,6 +890,58 @@ int cape_smpl_skin_tile(int32_t K, int32_t J);
 int cape_smpl_skin(const float *T, int64_t T_sample_stride, const float *basis, int32_t K, const float *coef, const float *G,
                    const int32_t *ell_joint, const float *ell_weight, int32_t ell_width, const float *transl, int32_t J,
                    int32_t V, int32_t N, float *out, int64_t out_sample_stride, void *stream);
+
+/*
+ * SMPL posing, backward (cape_amd/csrc/smpl/smpl_bwd.hip).  Given gV [N][V][3] on `out` and / or gJ [N][J][3] on `joints`
+ * (either may be absent), the gradients on T, pose, betas and transl of the forward above.  With v_p = T + basis . coef,
+ * M_v = sum_j W_vj G_j, out_v = M_v.rot v_p + M_v.t + transl:
+ *   q_v = M_v.rot^T gV_v                       the gradient on v_p, and the direct part of dT
+ *   gcoef_k = sum_v basis[k,:,v] . q_v         rows < B: betas; rows B + 9(j-1) + 3r + c: added to dR_j
+ *   dG_j = sum_v W_vj gV_v (x) [v_p; 1]        3 rows of 4
+ * and the chain from the leaves to the root, a parent taking its children in increasing joint order:
+ *   dA_j.rot += dG_j.rot - dG_j.t (x) Jn_j;  dA_j.t += dG_j.t + gJ_j;  dJn_j -= A_j.rot^T dG_j.t
+ *   dR_j = A_p.rot^T dA_j.rot;  dA_p.rot += dA_j.rot R_j^T + dA_j.t (x) (Jn_j - Jn_p);  dA_p.t += dA_j.t
+ *   dJn_j += A_p.rot^T dA_j.t, dJn_p -= the same            (root: dR_0 = dA_0.rot, dJn_0 += dA_0.t)
+ *   dpose_j = Rodrigues backward of dR_j (the series branch below |pose_j|^2 = 1e-6: exactly the generators at 0)
+ *   dbetas = gcoef[:B] + jshapedirs . dJn;  dtransl = sum_v gV_v + sum_j gJ_j;  dT_v = q_v + sum_j J_regressor[j][v] dJn_j
+ * cape_smpl_skin_bwd tiles like cape_smpl_skin (the basis is streamed once per tile of samples) and leaves, per sample and
+ * workgroup, one record [gcoef K | dG 12 J | sum gV 3] in the caller's workspace: sums over the lanes by a fixed wave tree,
+ * over the waves pairwise.  cape_smpl_joints_bwd adds the records in fp64 and runs the chain and Rodrigues backward in fp64
+ * on the forward's fp32 values, which it recomputes with the forward's own code.  No atomics, bitwise repeatable, no host
+ * synchronisation, no allocation.  Errors as for the forward entries.
+ */
+/* plan [3] (HOST): samples per workgroup, workgroups (records) per sample, floats per record = K + 12 J + 3 */
+int cape_smpl_skin_bwd_plan(int32_t K, int32_t J, int32_t V, int32_t N, int32_t *plan);
+/* bytes of cape_smpl_skin_bwd's workspace: 4 * N * plan[1] * plan[2]; negative: the CAPE_E* code */
+int64_t cape_smpl_skin_bwd_workspace_bytes(int32_t K, int32_t J, int32_t V, int32_t N);
+/* coef / G as cape_smpl_joints wrote them.  q [N][V][3] (NULL: not written) takes M_v.rot^T gV_v.  need_coef = 0 skips the
+ * gcoef sums (neither pose nor betas want a gradient) and leaves the records' first K floats unwritten. */
+int cape_smpl_skin_bwd(const float *T, int64_t T_sample_stride, const float *basis, int32_t K, const float *coef,
+                       const float *G, const int32_t *ell_joint, const float *ell_weight, int32_t ell_width, const float *gV,
+                       int64_t gV_sample_stride, int32_t J, int32_t V, int32_t N, int32_t need_coef, float *q,
+                       int64_t q_sample_stride, void *workspace, int64_t workspace_bytes, void *stream);
+/* one workgroup per sample.  partials / blocks: cape_smpl_skin_bwd's workspace and plan[1] (NULL: gV absent), coef_valid: it
+ * ran with need_coef (required for dpose and dbetas).  gJ NULL: absent.  dpose [N][3J], dbetas [N][B], dtransl [N][3],
+ * dJn [N][J][3]: each may be NULL (not wanted), not all. */
+int cape_smpl_joints_bwd(const float *T, int64_t T_sample_stride, const int32_t *jreg_rowptr, const int32_t *jreg_colidx,
+                         const float *jreg_vals, const float *pose, const float *betas, int32_t B, const float *jshapedirs,
+                         const int32_t *parents, int32_t J, int32_t V, int32_t N, const float *gJ, const void *partials,
+                         int32_t blocks, int32_t coef_valid, float *dpose, float *dbetas, float *dtransl, float *dJn,
+                         void *stream);
+/* dT[n][v] = q[n][v] (NULL: 0) + sum_j J_regressor[j][v] dJn[n][j]: a gather through the regressor's transpose, CSC of the
+ * [J, V] matrix (colptr [V+1], rowidx < J, checked at load with cape_csr_validate).  shared != 0: one rest body for every
+ * sample, dT [V][3] is the sum over the samples (fp64, in sample order). */
+int cape_smpl_jreg_bwd(const float *q, int64_t q_sample_stride, const int32_t *jregT_colptr, const int32_t *jregT_rowidx,
+                       const float *jregT_vals, const float *dJn, int32_t J, int32_t V, int32_t N, int32_t shared, float *dT,
+                       int64_t dT_sample_stride, void *stream);
+/* d_disp[n, v, :] = mask[v] * std[v, :] * g[n, v, :] */
+int cape_smpl_dress_bwd(const float *g, int64_t g_sample_stride, const float *std_, const float *mask, float *d_disp,
+                        int64_t d_sample_stride, int32_t N, int32_t V, void *stream);
+/* loss[n] = inv_weight_sum * sum_v weights[v] |pred[n][v] - target[n][v]|^2 (fp64 sums, one workgroup per sample) and
+ * grad[n][v] = 2 inv_weight_sum weights[v] (pred - target) (NULL: not written): the data term of CAPE.fit_posed */
+int cape_smpl_weighted_l2(const float *pred, int64_t pred_sample_stride, const float *target, int64_t target_sample_stride,
+                          const float *weights, float inv_weight_sum, int32_t N, int32_t V, float *loss, float *grad,
+                          int64_t grad_sample_stride, void *stream);
 
 /*
  * Per-vertex Euclidean error and its statistics (cape_amd/csrc/eval/vertex_error.hip): the auto-encoding error of

@@ -151,6 +151,26 @@ template <> struct cape_is_bf16<cape_bf16> { static constexpr bool value = true;
         if (e__ != hipSuccess) return (int)e__;      \
     } while (0)
 
+// Sum of v over a 256-thread block, T in {float, double, unsigned}: shuffle-down tree inside each of the four waves, then the
+// four wave sums in a fixed order.  red: four T of LDS; it may be reused for the next sum at once (the leading barrier).
+template <typename T>
+__device__ __forceinline__ T cape_block_sum256(T v, T *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    __syncthreads();
+    if (lane == 0) red[w] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// blocks of `block` threads for a grid-stride launch over `items`: at least one, at most `cap`
+inline int cape_grid_blocks(long long items, int block, int cap) {
+    long long b = (items + block - 1) / block;
+    if (b > cap) b = cap;
+    return (int)(b < 1 ? 1 : b);
+}
+
 __device__ __forceinline__ float cape_act(float v, int act) {
     switch (act) {
         case CAPE_ACT_LEAKY: return v > 0.f ? v : 0.2f * v;

@@ -28,26 +28,6 @@ struct Ranks {
     uint32_t r[MAXR];
 };
 
-__device__ __forceinline__ double block_sum256(double v, double *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
-__device__ __forceinline__ unsigned block_sum256u(unsigned v, unsigned *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __device__ __forceinline__ bool nonfinite_bits(unsigned u) { return (u & 0x7F800000u) == 0x7F800000u; }
 
 // Four consecutive elements starting at 4 * q: one 16-byte load where the buffer allows it (VEC: base 16-byte aligned) and the
@@ -104,8 +84,8 @@ __global__ __launch_bounds__(LB) void row_sum_kernel(const float *dist, int Vc, 
         s += (double)v;
         nf += nonfinite_bits(__float_as_uint(v)) ? 1u : 0u;
     }
-    s = block_sum256(s, red);
-    nf = block_sum256u(nf, redu);
+    s = cape_block_sum256(s, red);
+    nf = cape_block_sum256(nf, redu);
     if (threadIdx.x == 0) {
         rowsum[blockIdx.x] = s;
         rownf[blockIdx.x] = nf;
@@ -121,8 +101,8 @@ __global__ __launch_bounds__(LB) void final_kernel(const double *part, const uns
         s += part[i];
         if (cnt) c += (double)cnt[i];
     }
-    s = block_sum256(s, red);
-    if (cnt) c = block_sum256(c, red);
+    s = cape_block_sum256(s, red);
+    if (cnt) c = cape_block_sum256(c, red);
     if (threadIdx.x == 0) {
         out[0] = s / n;
         if (cnt) out_cnt[0] = c;
@@ -145,7 +125,7 @@ __global__ __launch_bounds__(LB) void var_kernel(const float *dist, long long n,
             s += e * e;
         }
     }
-    s = block_sum256(s, red);
+    s = cape_block_sum256(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -268,12 +248,6 @@ __global__ __launch_bounds__(LB) void select_scan_kernel(int R, int shift, int l
     }
 }
 
-inline int nblocks(long long items, int cap) {
-    long long b = (items + LB - 1) / LB;
-    if (b > cap) b = cap;
-    return (int)(b < 1 ? 1 : b);
-}
-
 inline int64_t align8(int64_t b) { return (b + 7) & ~(int64_t)7; }
 
 // workspace: [state | histogram R x NBINS | variance partials MAXB | row sums S | row non-finite counts S]
@@ -300,8 +274,8 @@ extern "C" int cape_vertex_error(const float *pred, int32_t ldp, const float *gt
     if (!pred || !gt || !std_ || !idx || !dist) return CAPE_EINVAL;
     if (N < 1 || V < 1 || Vc < 1 || S < 1 || Vc > V || ldp < 3 || row0 < 0) return CAPE_EINVAL;
     if ((int64_t)row0 + N > S || !sizes_ok(S, Vc)) return CAPE_EINVAL;
-    CAPE_LAUNCH(vertex_error_kernel, dim3(nblocks((long long)N * Vc, 4096)), dim3(LB), 0, (hipStream_t)stream, pred, ldp, gt, std_, idx,
-                N, V, Vc, dist, row0);
+    CAPE_LAUNCH(vertex_error_kernel, dim3(cape_grid_blocks((long long)N * Vc, LB, 4096)), dim3(LB), 0, (hipStream_t)stream, pred,
+                ldp, gt, std_, idx, N, V, Vc, dist, row0);
     CAPE_LAUNCH_CHECK();
     return CAPE_OK;
 }
@@ -336,7 +310,7 @@ extern "C" int cape_error_stats(const float *dist, int32_t S, int32_t Vc, const 
     CAPE_LAUNCH_CHECK();
     CAPE_LAUNCH(final_kernel, dim3(1), dim3(LB), 0, st, rowsum, rownf, S, (double)n, out_moments, out_moments + 2);
     CAPE_LAUNCH_CHECK();
-    const int nv = nblocks(quads, MAXB);
+    const int nv = cape_grid_blocks(quads, LB, MAXB);
     if (vec)
         CAPE_LAUNCH(var_kernel<true>, dim3(nv), dim3(LB), 0, st, dist, n, out_moments, varpart);
     else

@@ -1,24 +1,22 @@
-// L1 reconstruction loss + SMPL edge loss and their gradients w.r.t. the prediction
+// Reconstruction loss + SMPL edge loss and their gradients w.r.t. the prediction
 // (reference lib/models.py:357-360,374-375 and lib/losses.py:9-25):
 //   recon = mean |pred - gt|
 //   edge  = mean_e || ((pred+ref)_i - (pred+ref)_j) - ((gt+ref)_i - (gt+ref)_j) ||_2
-// The gradient is gathered per vertex from a vertex->incident-edge table (no float atomics;
-// deterministic).  d||d||/dd at d == 0 is defined as 0 (TF's tf.norm gradient is NaN there).
+// and the reference's loss_mask option (lib/models.py:47-52, 357-369), the mask handed to tf.losses.*(weights=...) with
+// Reduction.MEAN:
+//   recon = sum w * l(pred - gt) / sum w       (w the [V, 3] weights broadcast over the batch; the host passes 1 / sum w)
+//   l = |d| (l1), 0.5 d^2 if |d| <= 0.1 else 0.1 |d| - 0.005 (huber), d^2 (l2)
+//   d recon / d pred = w * l'(d) / sum w,  l'(0) = 0 for l1 (TF's sign), l'(d) = clip(d, -0.1, 0.1) for huber
+// Both entries run the same edge pass and the same finishing kernel, so the edge value and the edge part of the gradient
+// are the same bits with and without a mask.  The gradient is gathered per vertex from a vertex->incident-edge table (no
+// float atomics; deterministic).  d||d||/dd at d == 0 is defined as 0 (TF's tf.norm gradient is NaN there).
+#include <cmath>
+
 #include "common.h"
 
 namespace {
 
 constexpr int LB = 256;
-
-__device__ __forceinline__ float block_sum256(float v, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // per (n, e): unit difference vector -> unit[n,e,0:3], block-partial sum of lengths
 __global__ __launch_bounds__(LB) void edge_fwd_kernel(const float *pred, const float *gt, const float *ref, const int *edges,
@@ -48,14 +46,32 @@ __global__ __launch_bounds__(LB) void edge_fwd_kernel(const float *pred, const f
             unit[i * 3 + 2] = d[2] * inv;
         }
     }
-    s = block_sum256(s, red);
+    s = cape_block_sum256(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
-// per (n, v): L1 partial sums and the combined gradient
-__global__ __launch_bounds__(LB) void vert_kernel(const float *pred, const float *gt, const float *unit, const int *vptr,
-                                                  const int *vidx, int N, int M, int E, int ldp, int ldd, float cr, float ce,
-                                                  float *dpred, float *part) {
+// loss value l(d) and slope l'(d) of one coordinate; KIND 0 = l1, 1 = huber (delta 0.1), 2 = l2
+template <int KIND>
+__device__ __forceinline__ void pointwise_loss(float d, float &l, float &dl) {
+    if (KIND == 0) {
+        l = fabsf(d);
+        dl = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);
+    } else if (KIND == 1) {
+        const float a = fabsf(d);
+        l = a <= 0.1f ? 0.5f * a * a : 0.1f * a - 0.005f;
+        dl = fminf(fmaxf(d, -0.1f), 0.1f);
+    } else {
+        l = d * d;
+        dl = 2.f * d;
+    }
+}
+
+// per (n, v): partial sums of the point-wise loss and the combined gradient.  WEIGHTED: each coordinate times wts[v, k], and
+// cr = w_recon / sum w; otherwise wts is not read and cr = w_recon / (3 N M)
+template <int KIND, bool WEIGHTED>
+__device__ __forceinline__ void vert_body(const float *pred, const float *gt, const float *wts, const float *unit, const int *vptr,
+                                          const int *vidx, int N, int M, int E, int ldp, int ldd, float cr, float ce, float *dpred,
+                                          float *part) {
     __shared__ float red[4];
     const long long total = (long long)N * M;
     float s = 0.f;
@@ -66,8 +82,16 @@ __global__ __launch_bounds__(LB) void vert_kernel(const float *pred, const float
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             const float d = pred[i * ldp + k] - gt[i * 3 + k];
-            s += fabsf(d);
-            g[k] = cr * (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f));
+            float l, dl;
+            pointwise_loss<KIND>(d, l, dl);
+            if (WEIGHTED) {
+                const float w = wts[v * 3 + k];
+                s = fmaf(w, l, s);
+                g[k] = cr * (w * dl);
+            } else {
+                s += l;
+                g[k] = cr * dl;
+            }
         }
         if (dpred) {
             for (int t = vptr[v]; t < vptr[v + 1]; ++t) {
@@ -84,20 +108,34 @@ __global__ __launch_bounds__(LB) void vert_kernel(const float *pred, const float
             dpred[i * ldd + 2] = g[2];
         }
     }
-    s = block_sum256(s, red);
+    s = cape_block_sum256(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
+__global__ __launch_bounds__(LB) void vert_kernel(const float *pred, const float *gt, const float *unit, const int *vptr,
+                                                  const int *vidx, int N, int M, int E, int ldp, int ldd, float cr, float ce,
+                                                  float *dpred, float *part) {
+    vert_body<0, false>(pred, gt, nullptr, unit, vptr, vidx, N, M, E, ldp, ldd, cr, ce, dpred, part);
+}
+
+template <int KIND>
+__global__ __launch_bounds__(LB) void masked_vert_kernel(const float *pred, const float *gt, const float *wts, const float *unit,
+                                                         const int *vptr, const int *vidx, int N, int M, int E, int ldp, int ldd,
+                                                         float cr, float ce, float *dpred, float *part) {
+    vert_body<KIND, true>(pred, gt, wts, unit, vptr, vidx, N, M, E, ldp, ldd, cr, ce, dpred, part);
+}
+
+// one block: both sums in a fixed order, the two means (inv_v: 1 / (3 N M), or 1 / sum w of the weighted entry), the total
 __global__ __launch_bounds__(LB) void loss_final_kernel(const float *part_e, int ne, float inv_e, const float *part_v, int nv,
                                                         float inv_v, float *loss_out, float w_recon, float w_edge, float *total_out,
                                                         const float *term_a, float w_a, const float *term_b) {
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < nv; i += LB) s += part_v[i];
-    s = block_sum256(s, red);
+    s = cape_block_sum256(s, red);
     float t = 0.f;
     for (int i = threadIdx.x; i < ne; i += LB) t += part_e[i];
-    t = block_sum256(t, red);
+    t = cape_block_sum256(t, red);
     if (threadIdx.x == 0) {
         loss_out[0] = s * inv_v;
         loss_out[1] = t * inv_e;
@@ -166,10 +204,42 @@ __global__ __launch_bounds__(GAN_LB) void gan_bce_kernel(const float *fake, long
     }
 }
 
-inline int nblocks(long long total) {
-    long long b = (total + LB - 1) / LB;
-    if (b > 1024) b = 1024;
-    return (int)(b < 1 ? 1 : b);
+// Both entries: the shared argument checks, the workspace split, the three launches.  weights == nullptr: the unweighted l1
+// vertex pass; otherwise the weighted one of loss_kind.  cr: the gradient's scale of the point-wise slope; inv_v: the
+// reciprocal that turns the vertex sum into recon.
+int recon_edge_launch(const float *pred, int32_t ldp, const float *gt, const float *verts_ref, const int32_t *edges,
+                      const int32_t *vert_edge_ptr, const int32_t *vert_edge_idx, int32_t N, int32_t M, int32_t E,
+                      const float *weights, int32_t loss_kind, float cr, float inv_v, float w_recon, float w_edge, float *loss_out,
+                      float *total_out, const float *term_a, float w_a, const float *term_b, float *dpred, int32_t ldd,
+                      void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!pred || !gt || !verts_ref || !edges || !loss_out || !workspace || N < 1 || M < 1 || E < 1 || ldp < 3) return CAPE_EINVAL;
+    if (dpred && ldd < 3) return CAPE_EINVAL;
+    if (dpred && (!vert_edge_ptr || !vert_edge_idx)) return CAPE_EINVAL;
+    if (workspace_bytes < cape_recon_edge_workspace_bytes(N, M, E)) return CAPE_EWORKSPACE;
+    float *ws = (float *)workspace;
+    float *part_e = ws, *part_v = ws + 1024, *unit = ws + 2048;
+    hipStream_t st = (hipStream_t)stream;
+    const int ne = cape_grid_blocks((long long)N * E, LB, 1024), nv = cape_grid_blocks((long long)N * M, LB, 1024);
+    CAPE_LAUNCH(edge_fwd_kernel, dim3(ne), dim3(LB), 0, st, pred, gt, verts_ref, edges, N, M, E, ldp, unit, part_e);
+    CAPE_LAUNCH_CHECK();
+    const float ce = w_edge / ((float)N * (float)E);
+    if (!weights)
+        CAPE_LAUNCH(vert_kernel, dim3(nv), dim3(LB), 0, st, pred, gt, unit, vert_edge_ptr, vert_edge_idx, N, M, E, ldp, ldd, cr, ce,
+                    dpred, part_v);
+    else if (loss_kind == 0)
+        CAPE_LAUNCH(masked_vert_kernel<0>, dim3(nv), dim3(LB), 0, st, pred, gt, weights, unit, vert_edge_ptr, vert_edge_idx, N, M, E,
+                    ldp, ldd, cr, ce, dpred, part_v);
+    else if (loss_kind == 1)
+        CAPE_LAUNCH(masked_vert_kernel<1>, dim3(nv), dim3(LB), 0, st, pred, gt, weights, unit, vert_edge_ptr, vert_edge_idx, N, M, E,
+                    ldp, ldd, cr, ce, dpred, part_v);
+    else
+        CAPE_LAUNCH(masked_vert_kernel<2>, dim3(nv), dim3(LB), 0, st, pred, gt, weights, unit, vert_edge_ptr, vert_edge_idx, N, M, E,
+                    ldp, ldd, cr, ce, dpred, part_v);
+    CAPE_LAUNCH_CHECK();
+    CAPE_LAUNCH(loss_final_kernel, dim3(1), dim3(LB), 0, st, part_e, ne, 1.0f / ((float)N * (float)E), part_v, nv, inv_v, loss_out,
+                w_recon, w_edge, total_out, term_a, w_a, term_b);
+    CAPE_LAUNCH_CHECK();
+    return CAPE_OK;
 }
 
 }  // namespace
@@ -179,29 +249,32 @@ extern "C" int64_t cape_recon_edge_workspace_bytes(int32_t N, int32_t M, int32_t
     return ((int64_t)N * E * 3 + 2048) * (int64_t)sizeof(float);
 }
 
+extern "C" int64_t cape_masked_recon_edge_workspace_bytes(int32_t N, int32_t M, int32_t E) {
+    return cape_recon_edge_workspace_bytes(N, M, E);
+}
+
 extern "C" int cape_recon_edge_loss_fwd_bwd(const float *pred, int32_t ldp, const float *gt, const float *verts_ref, const int32_t *edges,
                                             const int32_t *vert_edge_ptr, const int32_t *vert_edge_idx, int32_t N, int32_t M,
                                             int32_t E, float w_recon, float w_edge, float *loss_out, float *total_out,
                                             const float *term_a, float w_a, const float *term_b, float *dpred, int32_t ldd,
                                             void *workspace, int64_t workspace_bytes, void *stream) {
-    if (!pred || !gt || !verts_ref || !edges || !loss_out || !workspace || N < 1 || M < 1 || E < 1 || ldp < 3) return CAPE_EINVAL;
-    if (dpred && ldd < 3) return CAPE_EINVAL;
-    if (dpred && (!vert_edge_ptr || !vert_edge_idx)) return CAPE_EINVAL;
-    if (workspace_bytes < cape_recon_edge_workspace_bytes(N, M, E)) return CAPE_EWORKSPACE;
-    float *ws = (float *)workspace;
-    float *part_e = ws, *part_v = ws + 1024, *unit = ws + 2048;
-    hipStream_t st = (hipStream_t)stream;
-    const int ne = nblocks((long long)N * E), nv = nblocks((long long)N * M);
-    CAPE_LAUNCH(edge_fwd_kernel, dim3(ne), dim3(LB), 0, st, pred, gt, verts_ref, edges, N, M, E, ldp, unit, part_e);
-    CAPE_LAUNCH_CHECK();
-    const float cr = w_recon / ((float)N * (float)M * 3.0f);
-    const float ce = w_edge / ((float)N * (float)E);
-    CAPE_LAUNCH(vert_kernel, dim3(nv), dim3(LB), 0, st, pred, gt, unit, vert_edge_ptr, vert_edge_idx, N, M, E, ldp, ldd, cr, ce, dpred, part_v);
-    CAPE_LAUNCH_CHECK();
-    CAPE_LAUNCH(loss_final_kernel, dim3(1), dim3(LB), 0, st, part_e, ne, 1.0f / ((float)N * (float)E), part_v, nv,
-                       1.0f / ((float)N * (float)M * 3.0f), loss_out, w_recon, w_edge, total_out, term_a, w_a, term_b);
-    CAPE_LAUNCH_CHECK();
-    return CAPE_OK;
+    const float nm3 = (float)N * (float)M * 3.0f;
+    return recon_edge_launch(pred, ldp, gt, verts_ref, edges, vert_edge_ptr, vert_edge_idx, N, M, E, nullptr, 0, w_recon / nm3,
+                             1.0f / nm3, w_recon, w_edge, loss_out, total_out, term_a, w_a, term_b, dpred, ldd, workspace,
+                             workspace_bytes, stream);
+}
+
+extern "C" int cape_masked_recon_edge_loss_fwd_bwd(const float *pred, int32_t ldp, const float *gt, const float *verts_ref,
+                                                   const int32_t *edges, const int32_t *vert_edge_ptr, const int32_t *vert_edge_idx,
+                                                   int32_t N, int32_t M, int32_t E, const float *weights, int32_t loss_kind,
+                                                   float inv_weight_sum, float w_recon, float w_edge, float *loss_out,
+                                                   float *total_out, const float *term_a, float w_a, const float *term_b,
+                                                   float *dpred, int32_t ldd, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!weights || loss_kind < 0 || loss_kind > 2) return CAPE_EINVAL;
+    if (!(inv_weight_sum > 0.f) || !std::isfinite(inv_weight_sum)) return CAPE_EINVAL;    // sum w > 0 and finite
+    return recon_edge_launch(pred, ldp, gt, verts_ref, edges, vert_edge_ptr, vert_edge_idx, N, M, E, weights, loss_kind,
+                             w_recon * inv_weight_sum, inv_weight_sum, w_recon, w_edge, loss_out, total_out, term_a, w_a, term_b,
+                             dpred, ldd, workspace, workspace_bytes, stream);
 }
 
 extern "C" int cape_gan_bce_fwd_bwd(const float *fake, int64_t fake_sample_stride, int32_t ldf, const float *real,

@@ -15,16 +15,6 @@ namespace {
 constexpr int LB = 256;
 constexpr int MAXB = 1024;
 
-__device__ __forceinline__ float block_sum256(float v, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0) red[w] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __device__ __forceinline__ void cross3(const float *a, const float *b, float *m) {
     m[0] = a[1] * b[2] - a[2] * b[1];
     m[1] = a[2] * b[0] - a[0] * b[2];
@@ -78,7 +68,7 @@ __global__ __launch_bounds__(LB) void normal_face_kernel(const float *pred, cons
             g[i * 3 + 2] = k * (ny[2] - c * nx[2]);
         }
     }
-    s = block_sum256(s, red);
+    s = cape_block_sum256(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -116,18 +106,12 @@ __global__ __launch_bounds__(LB) void normal_final_kernel(const float *part, int
     __shared__ float red[4];
     float s = 0.f;
     for (int i = threadIdx.x; i < nb; i += LB) s += part[i];
-    s = block_sum256(s, red);
+    s = cape_block_sum256(s, red);
     if (threadIdx.x == 0) {
         const float normal = s * inv_nf;
         loss_out[0] = normal;
         if (total_out) *total_out = fmaf(w_normal, normal, term_in ? *term_in : 0.f);
     }
-}
-
-inline int nblocks(long long total) {
-    long long b = (total + LB - 1) / LB;
-    if (b > MAXB) b = MAXB;
-    return (int)(b < 1 ? 1 : b);
 }
 
 }  // namespace
@@ -150,14 +134,14 @@ extern "C" int cape_face_normal_loss_fwd_bwd(const float *pred, int32_t ldp, con
     if (workspace_bytes < cape_face_normal_loss_workspace_bytes(N, M, F)) return CAPE_EWORKSPACE;
     float *part = (float *)workspace, *g = part + MAXB;
     hipStream_t st = (hipStream_t)stream;
-    const int nf = nblocks((long long)N * F);
+    const int nf = cape_grid_blocks((long long)N * F, LB, MAXB);
     const float inv_nf = 1.0f / ((float)N * (float)F);
     CAPE_LAUNCH(normal_face_kernel, dim3(nf), dim3(LB), 0, st, pred, gt, verts_ref, faces, N, M, F, ldp, w_normal * inv_nf,
                 dpred ? g : (float *)nullptr, part);
     CAPE_LAUNCH_CHECK();
     if (dpred) {
-        CAPE_LAUNCH(normal_vert_kernel, dim3(nblocks((long long)N * M)), dim3(LB), 0, st, pred, verts_ref, faces, vert_face_ptr,
-                    vert_face_idx, g, N, M, F, ldp, ldd, dpred);
+        CAPE_LAUNCH(normal_vert_kernel, dim3(cape_grid_blocks((long long)N * M, LB, MAXB)), dim3(LB), 0, st, pred, verts_ref, faces,
+                    vert_face_ptr, vert_face_idx, g, N, M, F, ldp, ldd, dpred);
         CAPE_LAUNCH_CHECK();
     }
     CAPE_LAUNCH(normal_final_kernel, dim3(1), dim3(LB), 0, st, part, nf, inv_nf, w_normal, loss_out, total_out, term_in);

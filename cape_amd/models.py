@@ -889,38 +889,27 @@ class CAPE(base_model):
         lat = self._latent_term(z_mean, z_logvar)
         reg = self._fc_regulariser()
         out['latent'], out['fc_reg_g'] = lat, reg
-        if self._loss_mask_w is not None and g_outputs.shape[-1] == 3:
-            # loss_mask (reference :357-369): every loss kind through the weighted kernel, sum w * l / sum w; latent and
-            # regulariser are folded in under the same conditions as in the l1 branch below
+        masked = self._loss_mask_w is not None
+        if (masked or self.which_loss == 'l1') and g_outputs.shape[-1] == 3:
+            # one device kernel: l1, or with loss_mask (reference :357-369) every loss kind as sum w * l / sum w
             vr, ed, vptr, vidx = self._edge_tables()
-            scalar = lambda t: torch.is_tensor(t) and t.dim() == 0 and t.is_cuda and t.dtype == torch.float32
-            reg_ok = (scalar(reg) and not reg.requires_grad) if torch.is_tensor(reg) else float(reg) == 0.0
-            kind = self.which_loss if self.which_loss in ('l1', 'huber') else 'l2'       # :367 else: mean_squared_error
-            args = (g_outputs, g_gt, vr, ed, vptr, vidx, self._loss_mask_dev(), self._loss_mask_sum, kind,
-                    float(self.lambda_l1), float(self.lambda_edge))
-            if g_outputs.is_cuda and scalar(lat) and reg_ok:
-                total, parts = ops.MaskedReconEdgeLossFn.apply(*args, lat, float(self.lambda_latent),
-                                                               reg if torch.is_tensor(reg) else None)
-                out['recon'], out['edge'], out['total_no_gan'] = parts[0], parts[1], total
-                return out
-            total_re, parts = ops.MaskedReconEdgeLossFn.apply(*args)
-            out['recon'], out['edge'] = parts[0], parts[1]
-        elif self.which_loss == 'l1' and g_outputs.shape[-1] == 3:
-            vr, ed, vptr, vidx = self._edge_tables()
+            weighted = ()
+            if masked:
+                kind = self.which_loss if self.which_loss in ('l1', 'huber') else 'l2'   # :367 else: mean_squared_error
+                weighted = (self._loss_mask_dev(), self._loss_mask_sum, kind)
             # the latent term and the regulariser value join the weighted sum INSIDE the loss kernel when they are device
             # scalars already (the fused sampling / KL op; the bucket path's detached regulariser): no element-wise launches
             # for  total_re + lambda_latent * latent + reg  and none for their gradients
             scalar = lambda t: torch.is_tensor(t) and t.dim() == 0 and t.is_cuda and t.dtype == torch.float32
             reg_ok = (scalar(reg) and not reg.requires_grad) if torch.is_tensor(reg) else float(reg) == 0.0
-            if g_outputs.is_cuda and scalar(lat) and reg_ok:
-                total, parts = ops.ReconEdgeLossFn.apply(g_outputs, g_gt, vr, ed, vptr, vidx, float(self.lambda_l1),
-                                                         float(self.lambda_edge), lat, float(self.lambda_latent),
-                                                         reg if torch.is_tensor(reg) else None)
-                out['recon'], out['edge'], out['total_no_gan'] = parts[0], parts[1], total
-                return out
-            total_re, parts = ops.ReconEdgeLossFn.apply(g_outputs, g_gt, vr, ed, vptr, vidx,
-                                                        float(self.lambda_l1), float(self.lambda_edge))
+            fold = g_outputs.is_cuda and scalar(lat) and reg_ok
+            terms = (lat, float(self.lambda_latent), reg if torch.is_tensor(reg) else None) if fold else (None, 0.0, None)
+            total_re, parts = ops.ReconEdgeLossFn.apply(g_outputs, g_gt, vr, ed, vptr, vidx, float(self.lambda_l1),
+                                                        float(self.lambda_edge), *terms, *weighted)
             out['recon'], out['edge'] = parts[0], parts[1]
+            if fold:
+                out['total_no_gan'] = total_re
+                return out
         else:
             diff = g_outputs - g_gt
             if self.which_loss == 'l1':

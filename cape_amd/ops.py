@@ -2046,25 +2046,51 @@ def _const_scalar(value, device):
     return t
 
 
+MASKED_LOSS_KIND = {'l1': 0, 'huber': 1, 'l2': 2}
+
+
+def _loss_pred_view(pred):
+    """(pred, ldp) for the loss kernels: the decoder's output is a [N, M, 3] view of 16-byte rows, read where it lies (no
+    re-homing launch); any other layout is made contiguous."""
+    N, M, _ = pred.shape
+    if pred.stride(2) != 1 or pred.stride(1) < 3 or (N > 1 and pred.stride(0) != M * pred.stride(1)):
+        pred = pred.contiguous()
+    return pred, (int(pred.stride(1)) if M > 1 else 3)
+
+
+def _is_unit_grad(gtotal):
+    """d(loss)/d(total) is the caller's constant 1 (UNIT_GRAD)."""
+    return UNIT_GRAD is not None and gtotal.data_ptr() == UNIT_GRAD.data_ptr()
+
+
+def _scaled_by(saved, gtotal):
+    """saved * gtotal: the gradient computed in forward, returned unscaled (no launch) when gtotal is the constant 1."""
+    return saved if _is_unit_grad(gtotal) else saved * gtotal
+
+
 class ReconEdgeLossFn(torch.autograd.Function):
-    """total = w_recon * mean|pred-gt| + w_edge * edge_loss [+ w_a * term_a + term_b]  (lib/models.py:357-375, 393-394,
+    """total = w_recon * recon + w_edge * edge_loss [+ w_a * term_a + term_b]  (lib/models.py:357-375, 393-394,
     lib/losses.py:9-25).  Returns (total, [recon, edge]); only ``total`` is differentiable.  ``term_a`` (a 0-dim tensor, e.g. the
     latent term; differentiable, its gradient is the constant w_a) and ``term_b`` (0-dim, a value without gradient: the
-    regulariser) are added by the kernel that finishes the loss, not by element-wise launches afterwards."""
+    regulariser) are added by the kernel that finishes the loss, not by element-wise launches afterwards.
+    Without ``weights``: recon = mean|pred-gt|.  With the reference's loss_mask (lib/models.py:47-52, 357-369):
+    recon = sum w * l(pred - gt) / sum w, l the l1 / huber / l2 loss of ``kind`` and w the per-vertex ``weights`` [M, 3] (fp32,
+    device) broadcast over the batch -- TF's Reduction.MEAN of the weighted loss.  ``weight_sum``: the host's sum of
+    ``weights`` (one sample); the kernel is handed 1 / (N * weight_sum)."""
 
     @staticmethod
-    def forward(ctx, pred, gt, verts_ref, edges, vptr, vidx, w_recon, w_edge, term_a=None, w_a=0.0, term_b=None):
+    def forward(ctx, pred, gt, verts_ref, edges, vptr, vidx, w_recon, w_edge, term_a=None, w_a=0.0, term_b=None, weights=None,
+                weight_sum=None, kind='l1'):
         _lib.require_gpu()
         gt = gt.contiguous()
         N, M, _ = pred.shape
-        # the decoder's output is a [N, M, 3] view of 16-byte rows: read it where it lies (no re-homing launch)
-        if pred.stride(2) != 1 or pred.stride(1) < 3 or (N > 1 and pred.stride(0) != M * pred.stride(1)):
-            pred = pred.contiguous()
-        ldp = int(pred.stride(1)) if M > 1 else 3
+        pred, ldp = _loss_pred_view(pred)
         E = edges.shape[0]
-        if L1_SIGN_TRACE is not None and w_recon != 0.0:
+        code = MASKED_LOSS_KIND[kind]
+        assert weights is not None or code == 0, "the unweighted kernel is l1 only"
+        if L1_SIGN_TRACE is not None and code == 0 and w_recon != 0.0:
             L1_SIGN_TRACE.append(torch.sign(pred.detach() - gt).cpu())       # the kernel takes the sign of the same fp32 difference
-        need = lib.cape_recon_edge_workspace_bytes(N, M, E)
+        need = lib.cape_recon_edge_workspace_bytes(N, M, E)                  # the weighted entry's is the same number
         ws = torch.empty((need + 3) // 4, device=pred.device, dtype=torch.float32)
         out = torch.empty(2, device=pred.device, dtype=torch.float32)
         total = torch.empty((), device=pred.device, dtype=torch.float32)
@@ -2072,12 +2098,19 @@ class ReconEdgeLossFn(torch.autograd.Function):
         ldd = int(dpred.stride(1))
         for t in (term_a, term_b):
             assert t is None or (t.dim() == 0 and t.dtype == torch.float32 and t.device == pred.device)
-        _log_launch("recon_edge_loss", 0, N * (E * 24 + M * 36),
-                    lambda: check(lib.cape_recon_edge_loss_fwd_bwd(_ptr(pred), ldp, _ptr(gt), _ptr(verts_ref), _ptr(edges), _ptr(vptr),
-                                                                   _ptr(vidx), N, M, E, float(w_recon), float(w_edge), _ptr(out),
-                                                                   _ptr(total), _ptr(term_a), float(w_a), _ptr(term_b), _ptr(dpred),
-                                                                   ldd, _ptr(ws), need, _stream()),
-                                  "cape_recon_edge_loss_fwd_bwd"))
+        head = (_ptr(pred), ldp, _ptr(gt), _ptr(verts_ref), _ptr(edges), _ptr(vptr), _ptr(vidx), N, M, E)
+        tail = (float(w_recon), float(w_edge), _ptr(out), _ptr(total), _ptr(term_a), float(w_a), _ptr(term_b), _ptr(dpred), ldd,
+                _ptr(ws), need, _stream())
+        if weights is None:
+            _log_launch("recon_edge_loss", 0, N * (E * 24 + M * 36),
+                        lambda: check(lib.cape_recon_edge_loss_fwd_bwd(*head, *tail), "cape_recon_edge_loss_fwd_bwd"))
+        else:
+            assert weights.shape == (M, 3) and weights.dtype == torch.float32 and weights.is_contiguous() \
+                and weights.device == pred.device
+            inv = 1.0 / (N * float(weight_sum))
+            _log_launch("masked_recon_edge_loss", 0, N * (E * 24 + M * 36) + M * 12,
+                        lambda: check(lib.cape_masked_recon_edge_loss_fwd_bwd(*head, _ptr(weights), code, inv, *tail),
+                                      "cape_masked_recon_edge_loss_fwd_bwd"))
         ctx.set_materialize_grads(False)         # no zeros for the non-differentiable parts' gradient
         ctx.save_for_backward(dpred)
         ctx.w_a = float(w_a) if term_a is not None else None
@@ -2088,69 +2121,21 @@ class ReconEdgeLossFn(torch.autograd.Function):
     def backward(ctx, gtotal, _gout):
         (dpred,) = ctx.saved_tensors
         if gtotal is None:
-            return (None,) * 11
-        unit = UNIT_GRAD is not None and gtotal.data_ptr() == UNIT_GRAD.data_ptr()      # d(loss)/d(total) is the caller's constant 1
+            return (None,) * 14
         ga = None
         if ctx.w_a is not None and ctx.needs_input_grad[8]:
-            ga = _const_scalar(ctx.w_a, dpred.device) if unit else gtotal * ctx.w_a
-        return (dpred if unit else dpred * gtotal), None, None, None, None, None, None, None, ga, None, None
+            ga = _const_scalar(ctx.w_a, dpred.device) if _is_unit_grad(gtotal) else gtotal * ctx.w_a
+        return (_scaled_by(dpred, gtotal),) + (None,) * 7 + (ga,) + (None,) * 5
 
 
-MASKED_LOSS_KIND = {'l1': 0, 'huber': 1, 'l2': 2}
-
-
-class MaskedReconEdgeLossFn(torch.autograd.Function):
-    """ReconEdgeLossFn with the reference's loss_mask (lib/models.py:47-52, 357-369): recon = sum w * l(pred - gt) / sum w,
-    l the l1 / huber / l2 loss of ``kind`` and w the per-vertex weights ``weights`` [M, 3] (fp32, device) broadcast over the
-    batch -- TF's Reduction.MEAN of the weighted loss.  ``weight_sum``: the host's sum of ``weights`` (one sample); the
-    kernel is handed 1 / (N * weight_sum).  Same outputs, same term_a / term_b folding, same gradient shortcut."""
+class MaskedReconEdgeLossFn:
+    """The weighted loss under its former name and argument order: forwards to ReconEdgeLossFn (no autograd node of its own)."""
 
     @staticmethod
-    def forward(ctx, pred, gt, verts_ref, edges, vptr, vidx, weights, weight_sum, kind, w_recon, w_edge, term_a=None, w_a=0.0,
-                term_b=None):
-        _lib.require_gpu()
-        gt = gt.contiguous()
-        N, M, _ = pred.shape
-        if pred.stride(2) != 1 or pred.stride(1) < 3 or (N > 1 and pred.stride(0) != M * pred.stride(1)):
-            pred = pred.contiguous()
-        ldp = int(pred.stride(1)) if M > 1 else 3
-        E = edges.shape[0]
-        assert weights.shape == (M, 3) and weights.dtype == torch.float32 and weights.is_contiguous() and weights.device == pred.device
-        code = MASKED_LOSS_KIND[kind]
-        if L1_SIGN_TRACE is not None and code == 0 and w_recon != 0.0:
-            L1_SIGN_TRACE.append(torch.sign(pred.detach() - gt).cpu())
-        need = lib.cape_masked_recon_edge_workspace_bytes(N, M, E)
-        ws = torch.empty((need + 3) // 4, device=pred.device, dtype=torch.float32)
-        out = torch.empty(2, device=pred.device, dtype=torch.float32)
-        total = torch.empty((), device=pred.device, dtype=torch.float32)
-        dpred = alloc_act(N, M, 3, pred.device, zero=False)
-        ldd = int(dpred.stride(1))
-        for t in (term_a, term_b):
-            assert t is None or (t.dim() == 0 and t.dtype == torch.float32 and t.device == pred.device)
-        inv = 1.0 / (N * float(weight_sum))
-        _log_launch("masked_recon_edge_loss", 0, N * (E * 24 + M * 36) + M * 12,
-                    lambda: check(lib.cape_masked_recon_edge_loss_fwd_bwd(_ptr(pred), ldp, _ptr(gt), _ptr(verts_ref), _ptr(edges),
-                                                                          _ptr(vptr), _ptr(vidx), N, M, E, _ptr(weights), code, inv,
-                                                                          float(w_recon), float(w_edge), _ptr(out), _ptr(total),
-                                                                          _ptr(term_a), float(w_a), _ptr(term_b), _ptr(dpred), ldd,
-                                                                          _ptr(ws), need, _stream()),
-                                  "cape_masked_recon_edge_loss_fwd_bwd"))
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(dpred)
-        ctx.w_a = float(w_a) if term_a is not None else None
-        ctx.mark_non_differentiable(out)
-        return total, out
-
-    @staticmethod
-    def backward(ctx, gtotal, _gout):
-        (dpred,) = ctx.saved_tensors
-        if gtotal is None:
-            return (None,) * 14
-        unit = UNIT_GRAD is not None and gtotal.data_ptr() == UNIT_GRAD.data_ptr()
-        ga = None
-        if ctx.w_a is not None and ctx.needs_input_grad[11]:
-            ga = _const_scalar(ctx.w_a, dpred.device) if unit else gtotal * ctx.w_a
-        return (dpred if unit else dpred * gtotal), None, None, None, None, None, None, None, None, None, None, ga, None, None
+    def apply(pred, gt, verts_ref, edges, vptr, vidx, weights, weight_sum, kind, w_recon, w_edge, term_a=None, w_a=0.0,
+              term_b=None):
+        return ReconEdgeLossFn.apply(pred, gt, verts_ref, edges, vptr, vidx, w_recon, w_edge, term_a, w_a, term_b, weights,
+                                     weight_sum, kind)
 
 
 class FaceNormalLossFn(torch.autograd.Function):
@@ -2166,9 +2151,7 @@ class FaceNormalLossFn(torch.autograd.Function):
         _lib.require_gpu()
         gt = gt.contiguous()
         N, M, _ = pred.shape
-        if pred.stride(2) != 1 or pred.stride(1) < 3 or (N > 1 and pred.stride(0) != M * pred.stride(1)):
-            pred = pred.contiguous()
-        ldp = int(pred.stride(1)) if M > 1 else 3
+        pred, ldp = _loss_pred_view(pred)
         F = faces.shape[0]
         assert pred.dtype == torch.float32 and gt.dtype == torch.float32 and gt.shape == (N, M, 3)
         assert faces.dtype == torch.int32 and faces.is_contiguous() and fidx.numel() == 3 * F and fptr.numel() == M + 1
@@ -2196,11 +2179,7 @@ class FaceNormalLossFn(torch.autograd.Function):
     def backward(ctx, gtotal, _gout):
         if gtotal is None:
             return (None,) * 8
-        unit = UNIT_GRAD is not None and gtotal.data_ptr() == UNIT_GRAD.data_ptr()
-        gp = None
-        if ctx.needs_input_grad[0]:
-            (dpred,) = ctx.saved_tensors
-            gp = dpred if unit else dpred * gtotal
+        gp = _scaled_by(ctx.saved_tensors[0], gtotal) if ctx.needs_input_grad[0] else None
         # d total / d term_in = 1: the incoming gradient itself, so that the op which produced term_in still recognises UNIT_GRAD
         gt_in = gtotal if (ctx.has_term and ctx.needs_input_grad[7]) else None
         return gp, None, None, None, None, None, None, gt_in

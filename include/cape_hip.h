@@ -615,7 +615,7 @@ int cape_recon_edge_loss_fwd_bwd(const float *pred, int32_t ldp, const float *gt
                                  int32_t ldd, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
- * Weighted reconstruction + edge loss (cape_amd/csrc/loss_mask/masked_loss.hip): the reference's loss_mask option
+ * Weighted reconstruction + edge loss (cape_amd/csrc/loss.hip): the reference's loss_mask option
  * (lib/models.py:47-52, 357-369), a per-vertex weight passed to tf.losses.absolute_difference / huber_loss /
  * mean_squared_error as weights= with Reduction.MEAN, which divides the weighted sum by the sum of the broadcast weights:
  *   d = pred - gt [N, M, 3];  w = weights [M, 3] broadcast over the N samples;  inv_weight_sum = 1 / (N * sum weights)

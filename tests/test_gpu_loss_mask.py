@@ -1,4 +1,4 @@
-"""loss_mask on the device: the weighted reconstruction + edge loss (cape_amd/csrc/loss_mask/masked_loss.hip) against fp64
+"""loss_mask on the device: the weighted reconstruction + edge loss (the weighted entry of cape_amd/csrc/loss.hip) against fp64
 torch autograd of its definition, recon = sum w * l(pred - gt) / sum w (TF's Reduction.MEAN of the weighted loss, reference
 lib/models.py:47-52, 357-369), and the model, the captured step and the drivers with a mask set."""
 import os
@@ -75,8 +75,9 @@ def _masked(pred_dev, gt, w, kind, tabs, w_recon=0.7, w_edge=1.3, terms=()):
     dev = pred_dev.device
     wt = torch.tensor(w, dtype=torch.float32, device=dev)
     wsum = float(wt.double().sum())
-    return ops.MaskedReconEdgeLossFn.apply(pred_dev, torch.tensor(gt, dtype=torch.float32, device=dev), *tabs, wt, wsum, kind,
-                                           w_recon, w_edge, *terms)
+    term_a, w_a, term_b = terms if terms else (None, 0.0, None)
+    return ops.ReconEdgeLossFn.apply(pred_dev, torch.tensor(gt, dtype=torch.float32, device=dev), *tabs, w_recon, w_edge,
+                                     term_a, w_a, term_b, wt, wsum, kind)
 
 
 @pytest.mark.parametrize("N", [1, 16])

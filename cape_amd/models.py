@@ -1521,79 +1521,85 @@ class CAPE(base_model):
         t_step = (time.time() - t_start) / max(num_steps, 1)
         return losses, t_step
 
-    def _pad(self, arr, begin, end, width_shape):
-        out = np.zeros((self.batch_size,) + tuple(width_shape))
-        tmp = arr[begin:end]
-        out[:end - begin] = self._dense_np(tmp)
+    def _batches(self, size):
+        """(begin, end) of the batches of ``batch_size`` rows that cover ``range(size)`` in order; the last may be short."""
+        for begin in range(0, size, self.batch_size):
+            yield begin, min(begin + self.batch_size, size)
+
+    def _padded_np(self, arr, begin, end):
+        """The padded batch every driver feeds the network, on the host: a float32 block of ``batch_size`` rows with rows
+        begin:end of ``arr`` (numpy or scipy.sparse) in front and zeros behind (reference :1035-1046).  An array of ONE row
+        stands for all samples -- one condition, many z samples (reference :1155-1158) -- and is repeated into the valid rows."""
+        out = np.zeros((self.batch_size,) + tuple(arr.shape[1:]), np.float32)
+        out[:end - begin] = self._dense_np(arr[0:1] if arr.shape[0] == 1 else arr[begin:end])
         return out
 
-    def encode(self, data=None, cond=None, cond2=None):
-        size = data.shape[0]
-        self._get_session()
-        self._begin_pass()
-        zs = [[], [], [], []]
-        with torch.no_grad():
-            for begin in range(0, size, self.batch_size):
-                end = min(begin + self.batch_size, size)
-                bd = self._dev(self._pad(data, begin, end, data.shape[1:]))
-                bc = self._dev(self._pad(cond, begin, end, cond.shape[1:]))
-                bc2 = self._dev(self._pad(cond2, begin, end, cond2.shape[1:]))
-                y, y2 = self._conditions(bc, bc2)
-                with self.variable_scope('generator'):
-                    zm, zv = self.encoder(bd, y, y2, use_res_block=self.use_res_block, use_cond=self.cond_encoder)
-                for lst, t in zip(zs, (zm, zv, y, y2)):
-                    lst.append(t[:end - begin].cpu().numpy())
-        return tuple(np.concatenate(l, 0) for l in zs)
+    def _padded(self, arr, begin, end):
+        return torch.from_numpy(self._padded_np(arr, begin, end)).to(self.device)
 
-    def encode_only_condition(self, cond=None, cond2=None):
-        size = cond.shape[0]
-        self._get_session()
-        self._begin_pass()
-        zc, zc2 = [], []
-        with torch.no_grad():
-            for begin in range(0, size, self.batch_size):
-                end = min(begin + self.batch_size, size)
-                bc = self._dev(self._pad(cond, begin, end, cond.shape[1:]))
-                bc2 = self._dev(self._pad(cond2, begin, end, cond2.shape[1:]))
-                y, y2 = self._conditions(bc, bc2)
-                zc.append(y[:end - begin].cpu().numpy())
-                zc2.append(y2[:end - begin].cpu().numpy())
-        return np.concatenate(zc, 0), np.concatenate(zc2, 0)
-
-    def predict(self, data, cond=None, cond2=None, labels=None, sess=None, phase='train'):
-        loss_recon, loss_latent, loss_edge = [], [], []
-        size = data.shape[0]
-        # float division, as in the reference (:1039; quirk C8)
-        num_zero_phs = self.batch_size * (size / self.batch_size + 1) - size
+    def _open_pass(self, sess=None):
+        """What every inference and fitting driver does once, before its loop and before it touches the device."""
         self._get_session(sess)
         self._begin_pass()
-        preds = []
+
+    def _embedded(self, size, cond, cond2):
+        """(begin, end, y, y2) per padded batch: the condition embeddings on the device."""
+        for begin, end in self._batches(size):
+            yield (begin, end) + self._conditions(self._padded(cond, begin, end), self._padded(cond2, begin, end))
+
+    def encode(self, data=None, cond=None, cond2=None):
+        self._open_pass()
+        zs = []
         with torch.no_grad():
-            for begin in range(0, size, self.batch_size):
-                end = min(begin + self.batch_size, size)
-                bd = self._dev(self._pad(data, begin, end, data.shape[1:]))
-                bc = self._dev(self._pad(cond, begin, end, cond.shape[1:]))
-                bc2 = self._dev(self._pad(cond2, begin, end, cond2.shape[1:]))
-                y, y2 = self._conditions(bc, bc2)
-                x_hat, zm, zv = self.generator(bd, y, y2)
-                if labels is not None:
-                    bl = self._dev(self._pad(labels, begin, end, labels.shape[1:]))
-                    lt = self.loss_terms(x_hat, bl, zm, zv)
-                    loss_recon.append(float(lt['recon']))
-                    loss_latent.append(float(lt['latent']))
-                    loss_edge.append(float(lt['edge']))
+            for begin, end, y, y2 in self._embedded(data.shape[0], cond, cond2):
+                with self.variable_scope('generator'):
+                    zm, zv = self.encoder(self._padded(data, begin, end), y, y2, use_res_block=self.use_res_block,
+                                          use_cond=self.cond_encoder)
+                zs.append([t[:end - begin].cpu().numpy() for t in (zm, zv, y, y2)])
+        return tuple(np.concatenate(l, 0) for l in zip(*zs))
+
+    def encode_only_condition(self, cond=None, cond2=None):
+        self._open_pass()
+        zs = []
+        with torch.no_grad():
+            for begin, end, y, y2 in self._embedded(cond.shape[0], cond, cond2):
+                zs.append([t[:end - begin].cpu().numpy() for t in (y, y2)])
+        return tuple(np.concatenate(l, 0) for l in zip(*zs))
+
+    def _generated(self, data, cond, cond2, labels):
+        """predict's and test_errors' loop: (begin, end, x_hat, labels_batch, loss_terms) per padded batch, all on the device;
+        the last two are None without ``labels``.  The generator draws its eps here, once per batch."""
+        for begin, end, y, y2 in self._embedded(data.shape[0], cond, cond2):
+            x_hat, zm, zv = self.generator(self._padded(data, begin, end), y, y2)
+            bl = lt = None
+            if labels is not None:
+                bl = self._padded(labels, begin, end)
+                lt = self.loss_terms(x_hat, bl, zm, zv)
+            yield begin, end, x_hat, bl, lt
+
+    def _loss_averages(self, terms, size):
+        """(recon, latent, edge) averaged over ``size`` samples from the per-batch loss_terms the way the reference does it
+        (:1083-1086, quirk C8): the last batch is taken as zero-padded and weighs ``batch_size - num_zero_phs``, and with the
+        float division of :1039 ``num_zero_phs`` is ``batch_size``: that weight is 0 up to rounding.  The scalars stayed on the
+        device until here (nothing synchronises for them inside the loop) and come back in one copy."""
+        # float64 holds an fp32 scalar, an fp64 one and a Python float alike exactly
+        scal = lambda t: (t if torch.is_tensor(t) else torch.tensor(float(t), dtype=torch.float64)).reshape(()).double().to(self.device)
+        per_batch = torch.stack([torch.stack([scal(lt[k]) for lt in terms]) for k in ('recon', 'latent', 'edge')]).cpu().numpy()
+        num_zero_phs = self.batch_size * (size / self.batch_size + 1) - size
+        return tuple((np.sum(c[:-1]) * self.batch_size + float(c[-1]) * (self.batch_size - num_zero_phs)) / size
+                     for c in per_batch)
+
+    def predict(self, data, cond=None, cond2=None, labels=None, sess=None, phase='train'):
+        self._open_pass(sess)
+        preds, terms = [], []
+        with torch.no_grad():
+            for begin, end, x_hat, _, lt in self._generated(data, cond, cond2, labels):
+                terms.append(lt)
                 preds.append(x_hat[:end - begin].cpu().numpy())
-        predictions = np.concatenate(preds, 0)
-
-        def calc_mean(coll):
-            last = coll[-1]
-            total = np.sum(np.array(coll)[:-1]) * self.batch_size + last * (self.batch_size - num_zero_phs)
-            return total / size
-
-        if labels is not None:
-            lr_, ll_, le_ = (calc_mean(c) for c in (loss_recon, loss_latent, loss_edge))
-            return predictions, lr_, ll_, le_
-        return predictions
+            predictions = np.concatenate(preds, 0)
+            if labels is None:
+                return predictions
+            return (predictions,) + self._loss_averages(terms, data.shape[0])
 
     def evaluate(self, data, cond=None, cond2=None, labels=None, sess=None):
         t_start = time.time()
@@ -1621,80 +1627,44 @@ class CAPE(base_model):
         sd, idx, qs = ops.error_arguments(self.input_num_verts, self.nn_input_channel, size, std, clothing_idx, quantiles)
         if labels is None:
             labels = data
-        loss_recon, loss_latent, loss_edge = [], [], []
-        num_zero_phs = self.batch_size * (size / self.batch_size + 1) - size      # as predict (quirk C8)
-        self._get_session()
-        self._begin_pass()
+        self._open_pass()
         sd_dev = torch.tensor(sd, dtype=torch.float32, device=self.device)
         idx_dev = torch.tensor(idx, dtype=torch.int32, device=self.device)
         dist = torch.empty((size, idx.size), dtype=torch.float32, device=self.device)
+        terms = []
         with torch.no_grad():
-            for begin in range(0, size, self.batch_size):
-                end = min(begin + self.batch_size, size)
-                bd = self._dev(self._pad(data, begin, end, data.shape[1:]))
-                bc = self._dev(self._pad(cond, begin, end, cond.shape[1:]))
-                bc2 = self._dev(self._pad(cond2, begin, end, cond2.shape[1:]))
-                y, y2 = self._conditions(bc, bc2)
-                x_hat, zm, zv = self.generator(bd, y, y2)
-                bl = self._dev(self._pad(labels, begin, end, labels.shape[1:]))
-                lt = self.loss_terms(x_hat, bl, zm, zv)
-                # the three scalars stay on the device until the end: no synchronisation inside the loop
-                loss_recon.append(lt['recon'])
-                loss_latent.append(lt['latent'])
-                loss_edge.append(lt['edge'])
+            for begin, end, x_hat, bl, lt in self._generated(data, cond, cond2, labels):
+                terms.append(lt)
                 xv = x_hat[:end - begin]
                 ops.vertex_error(xv if xv.dtype == torch.float32 else xv.float(), bl[:end - begin], sd_dev, idx_dev, dist,
                                  row0=begin)
             res = ops.error_statistics(dist, qs)
-            # float64 holds an fp32 scalar, an fp64 one and a Python float alike exactly: float() of it is predict's float(term)
-            scal = lambda t: (t if torch.is_tensor(t) else torch.tensor(float(t), dtype=torch.float64)).reshape(()).double().to(self.device)
-            losses = torch.stack([torch.stack([scal(t) for t in coll])
-                                  for coll in (loss_recon, loss_latent, loss_edge)]).cpu().numpy()
-
-        def calc_mean(coll):
-            coll = [float(v) for v in coll]
-            last = coll[-1]
-            total = np.sum(np.array(coll)[:-1]) * self.batch_size + last * (self.batch_size - num_zero_phs)
-            return total / size
-
-        res['recon'], res['latent'], res['edge'] = (calc_mean(c) for c in losses)
+            res['recon'], res['latent'], res['edge'] = self._loss_averages(terms, size)
         del res['order_ranks'], res['order_values'], res['euclidean_var']
         if return_distances:
             res['distances'] = dist.cpu().numpy()
         return res
 
-    def decode(self, data, cond=None, cond2=None):
-        size = data.shape[0]
-        self._get_session()
-        self._begin_pass()
-        recs = []
-        with torch.no_grad():
-            for begin in range(0, size, self.batch_size):
-                end = min(begin + self.batch_size, size)
-                bz = self._dev(self._pad(data, begin, end, data.shape[1:]))
-                bc = np.zeros((self.batch_size, cond.shape[1]))
-                bc2 = np.zeros((self.batch_size, cond2.shape[1]))
-                if cond.shape[0] == 1:      # one condition, many z samples (reference :1155-1158)
-                    bcond, econd = 0, self.batch_size
-                else:
-                    bcond, econd = begin, end
-                bc[:end - begin] = cond[bcond:econd]
-                bc2[:end - begin] = cond2[bcond:econd]
-                with self.variable_scope('generator'):
-                    x = self.decoder_cond_vert(bz, self._dev(bc), self._dev(bc2), use_res_block=self.use_res_block_dec)
-                recs.append(x[:end - begin].cpu().numpy())
-        return np.concatenate(recs, 0)
+    def _decoded(self, data, cond, cond2):
+        """decode's loop: (begin, end, x) per padded batch, ``x`` the decoder's output for all ``batch_size`` rows on the
+        device.  One condition row stands for every z sample (``_padded_np``)."""
+        for begin, end in self._batches(data.shape[0]):
+            bz, bc, bc2 = (self._padded(a, begin, end) for a in (data, cond, cond2))
+            with self.variable_scope('generator'):
+                x = self.decoder_cond_vert(bz, bc, bc2, use_res_block=self.use_res_block_dec)
+            yield begin, end, x
 
-    def decode_posed(self, data, cond, cond2, pose, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None):
-        """``decode`` followed by demos.py's posing step (:155-161 / :207-213 dress, :267-283 / :312-326 SMPL forward), on
-        the device per padded batch: decoder -> cape_smpl_dress -> cape_smpl_joints -> cape_smpl_skin.  ``pose`` [size, 72]
-        or [1, 72] (one pose for every sample), ``transl`` likewise or None; ``body_model`` a ``cape_amd.smpl.SMPL`` (or the
-        object ``cape_amd.smpl.create`` returns); ``minimal_shape`` defaults to the template mesh.  Batching, padding and the
-        one-condition-many-samples rule are decode's.  Returns (posed, clothed_unposed) [size, V, 3] float32."""
+    def decode(self, data, cond=None, cond2=None):
+        self._open_pass()
+        with torch.no_grad():
+            return np.concatenate([x[:end - begin].cpu().numpy() for begin, end, x in self._decoded(data, cond, cond2)], 0)
+
+    def _posed_arguments(self, size, body_model, pose, transl, dress, cond=None, cond2=None):
+        """What decode_posed and fit_posed share of their arguments: the body model, ``pose`` [1 or size, 3J] and ``transl``
+        [1 or size, 3] (or None) as float32, ``cond`` / ``cond2`` (when given: one row or one per sample, the same for both)
+        as float32, and the dressing arrays of ``dress`` = (mean, std, clothing_idx, minimal_shape) on the device."""
         from . import smpl as smpl_mod
         body = getattr(body_model, 'model', body_model)
-        size = data.shape[0]
-        V = body.V
         pose = np.asarray(pose, dtype=np.float32).reshape(-1, 3 * body.J)
         if pose.shape[0] not in (1, size):
             raise ValueError("pose: %d rows for %d samples" % (pose.shape[0], size))
@@ -1702,30 +1672,31 @@ class CAPE(base_model):
             transl = np.asarray(transl, dtype=np.float32).reshape(-1, 3)
             if transl.shape[0] not in (1, size):
                 raise ValueError("transl: %d rows for %d samples" % (transl.shape[0], size))
-        rows = lambda a, b, e: None if a is None else (np.repeat(a, e - b, 0) if a.shape[0] == 1 else a[b:e])
+        if cond is not None:
+            cond, cond2 = np.asarray(cond, dtype=np.float32), np.asarray(cond2, dtype=np.float32)
+            if cond.shape[0] not in (1, size) or cond2.shape[0] != cond.shape[0]:
+                raise ValueError("cond / cond2: one row, or one per sample")
+        mean, std, clothing_idx, minimal_shape = dress
         dressing = smpl_mod._DressArrays(mean, std, clothing_idx, self.verts_ref if minimal_shape is None else minimal_shape,
-                                         V, self.device)
-        self._get_session()
-        self._begin_pass()
+                                         body.V, self.device)
+        return body, pose, transl, dressing, cond, cond2
+
+    def decode_posed(self, data, cond, cond2, pose, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None):
+        """``decode`` followed by demos.py's posing step (:155-161 / :207-213 dress, :267-283 / :312-326 SMPL forward), on
+        the device per padded batch: decoder -> cape_smpl_dress -> cape_smpl_joints -> cape_smpl_skin.  ``pose`` [size, 72]
+        or [1, 72] (one pose for every sample), ``transl`` likewise or None; ``body_model`` a ``cape_amd.smpl.SMPL`` (or the
+        object ``cape_amd.smpl.create`` returns); ``minimal_shape`` defaults to the template mesh.  Batching, padding and the
+        one-condition-many-samples rule are decode's.  Returns (posed, clothed_unposed) [size, V, 3] float32."""
+        body, pose, transl, dressing, _, _ = self._posed_arguments(data.shape[0], body_model, pose, transl,
+                                                                   (mean, std, clothing_idx, minimal_shape))
+        self._open_pass()
         posed, clothed = [], []
         with torch.no_grad():
-            for begin in range(0, size, self.batch_size):
-                end = min(begin + self.batch_size, size)
-                bz = self._dev(self._pad(data, begin, end, data.shape[1:]))
-                bc = np.zeros((self.batch_size, cond.shape[1]))
-                bc2 = np.zeros((self.batch_size, cond2.shape[1]))
-                if cond.shape[0] == 1:      # one condition, many z samples (reference :1155-1158)
-                    bcond, econd = 0, self.batch_size
-                else:
-                    bcond, econd = begin, end
-                bc[:end - begin] = cond[bcond:econd]
-                bc2[:end - begin] = cond2[bcond:econd]
-                with self.variable_scope('generator'):
-                    x = self.decoder_cond_vert(bz, self._dev(bc), self._dev(bc2), use_res_block=self.use_res_block_dec)
-                x = x[:end - begin].float().contiguous()
-                T = dressing(x)
-                bt = rows(transl, begin, end)
-                vo, _ = body.forward(T, self._dev(rows(pose, begin, end)), None, None if bt is None else self._dev(bt))
+            for begin, end, x in self._decoded(data, cond, cond2):
+                nb = end - begin
+                T = dressing(x[:nb].float().contiguous())
+                vo, _ = body.forward(T, self._padded(pose, begin, end)[:nb], None,
+                                     None if transl is None else self._padded(transl, begin, end)[:nb])
                 posed.append(vo.cpu().numpy())
                 clothed.append(T.cpu().numpy())
         return np.concatenate(posed, 0), np.concatenate(clothed, 0)
@@ -1755,25 +1726,16 @@ class CAPE(base_model):
         Returns a dict: ``z`` [size, nz], ``pose`` [size, 3J], ``transl`` [size, 3] or None, ``posed`` / ``clothed``
         [size, V, 3] for the returned leaves, ``loss`` [steps + 1, size] the data term per sample (row 0: before the first
         update)."""
-        import ctypes as C
         from . import smpl as smpl_mod
         body = getattr(body_model, 'model', body_model)
         target = np.asarray(target, dtype=np.float32)
-        size, V, J, bs, nz = target.shape[0], body.V, body.J, self.batch_size, int(self.nz)
+        size, V, bs, nz = target.shape[0], body.V, self.batch_size, int(self.nz)
         if target.shape != (size, V, 3):
             raise ValueError("target: [size, %d, 3] expected, got %s" % (V, target.shape))
-        pose = np.asarray(pose, dtype=np.float32).reshape(-1, 3 * J)
-        if pose.shape[0] not in (1, size):
-            raise ValueError("pose: %d rows for %d samples" % (pose.shape[0], size))
         if transl is None and optimize_transl:
             transl = np.zeros((size, 3), np.float32)
-        if transl is not None:
-            transl = np.asarray(transl, dtype=np.float32).reshape(-1, 3)
-            if transl.shape[0] not in (1, size):
-                raise ValueError("transl: %d rows for %d samples" % (transl.shape[0], size))
-        cond, cond2 = np.asarray(cond, dtype=np.float32), np.asarray(cond2, dtype=np.float32)
-        if cond.shape[0] not in (1, size) or cond2.shape[0] != cond.shape[0]:
-            raise ValueError("cond / cond2: one row, or one per sample")
+        _, pose, transl, dressing, cond, cond2 = self._posed_arguments(size, body, pose, transl,
+                                                                       (mean, std, clothing_idx, minimal_shape), cond, cond2)
         z0 = np.zeros((size, nz), np.float32) if z0 is None else np.asarray(z0, dtype=np.float32)
         if z0.shape != (size, nz):
             raise ValueError("z0: [%d, %d] expected" % (size, nz))
@@ -1782,24 +1744,12 @@ class CAPE(base_model):
             raise ValueError("weights: [%d] with a positive sum expected" % V)
         steps = int(steps)
         inv_wsum = 1.0 / float(w.astype(np.float64).sum())
-        rows = lambda a, b, e: np.repeat(a, e - b, 0) if a.shape[0] == 1 else a[b:e]
-
-        def padded(a, b, e):            # rows b..e of a (one row: repeated) in a zero block of batch_size rows
-            out = np.zeros((bs,) + a.shape[1:], np.float32)
-            out[:e - b] = rows(a, b, e)
-            return self._dev(out)
-
-        dressing = smpl_mod._DressArrays(mean, std, clothing_idx, self.verts_ref if minimal_shape is None else minimal_shape,
-                                         V, self.device)
         w_dev = self._dev(w)
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        self._get_session()
-        self._begin_pass()
+        self._open_pass()
         if lambda_edge:
             _, ed, vptr, vidx = self._edge_tables()
             no_ref = torch.zeros((V, 3), dtype=torch.float32, device=self.device)
         res = dict(z=[], pose=[], transl=[], posed=[], clothed=[], loss=[])
-        stream = lambda: C.c_void_p(torch.cuda.current_stream().cuda_stream)
         # the model's variables are constants here: no gradient bucket to write into and, while the steps run, nothing that
         # requires a gradient (the ops then skip their weight-gradient kernels)
         grad_views, self._grad_views = self._grad_views, {}
@@ -1810,15 +1760,13 @@ class CAPE(base_model):
                 v.requires_grad_(not on)
 
         try:
-            for begin in range(0, size, bs):
-                end = min(begin + bs, size)
+            for begin, end in self._batches(size):
                 nb = end - begin
-                z = padded(z0, begin, end).requires_grad_(True)
-                bc = padded(cond, begin, end) if cond.shape[0] > 1 else self._dev(np.repeat(cond, bs, 0))
-                bc2 = padded(cond2, begin, end) if cond2.shape[0] > 1 else self._dev(np.repeat(cond2, bs, 0))
-                bp = padded(pose, begin, end).requires_grad_(bool(optimize_pose))
-                bt = None if transl is None else padded(transl, begin, end).requires_grad_(bool(optimize_transl))
-                tgt = padded(target, begin, end)
+                # one condition row stands for every sample, in the valid rows only: the batches decode_posed feeds the decoder
+                z, bc, bc2, bp, tgt = (self._padded(a, begin, end) for a in (z0, cond, cond2, pose, target))
+                z.requires_grad_(True)
+                bp.requires_grad_(bool(optimize_pose))
+                bt = None if transl is None else self._padded(transl, begin, end).requires_grad_(bool(optimize_transl))
                 leaves = [z] + ([bp] if optimize_pose else []) + ([bt] if optimize_transl else [])
                 opt = torch.optim.Adam(leaves, lr=float(lr))
                 loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
@@ -1829,9 +1777,7 @@ class CAPE(base_model):
                         x = self.decoder_cond_vert(torch.cat([z, bc, bc2], 1), bc, bc2, use_res_block=self.use_res_block_dec)
                     T = dressing.diff(x.float().contiguous())
                     posed, _ = body.forward_diff(T, bp, None, bt)
-                    _lib.check(_lib.lib.cape_smpl_weighted_l2(ptr(posed), 3 * V, ptr(tgt), 3 * V, ptr(w_dev), inv_wsum, nb, V,
-                                                              ptr(loss[step]), ptr(grad) if want_grad else None, 3 * V, stream()),
-                               "cape_smpl_weighted_l2")
+                    smpl_mod.weighted_l2(posed, tgt, w_dev, inv_wsum, nb, loss[step], grad if want_grad else None)
                     return T, posed
 
                 freeze(True)

@@ -8,6 +8,7 @@ bodies (reference demos.py:155-161, 207-213 and :249-331, which go through ``smp
   SMPL.pose(...)             the same on numpy arrays
   dress(...)                 de-normalise + clothing mask + minimal body (cape_smpl_dress)
   dress_diff(...)            the same with a gradient to the displacements (cape_smpl_dress_bwd)
+  weighted_l2(...)           per-sample weighted squared distance to target meshes and its gradient (cape_smpl_weighted_l2)
   create(...), body_models   an ``smplx``-compatible factory: with a one-line ``smplx.py`` in the reference checkout
                              (``from cape_amd.smpl import body_models``) demos.py poses through the device unchanged
 
@@ -364,6 +365,15 @@ def dress(disp, mean, std, clothing_idx, minimal_shape):
 def dress_diff(disp, mean, std, clothing_idx, minimal_shape):
     """``dress`` with a gradient to ``disp``."""
     return _DressArrays(mean, std, clothing_idx, minimal_shape, disp.shape[1], disp.device).diff(disp)
+
+
+def weighted_l2(posed, target, w, inv_wsum, n, loss_out, grad_out=None):
+    """The data term of ``CAPE.fit_posed`` for the first ``n`` samples of ``posed`` / ``target`` (contiguous float32 [N,V,3] on
+    the device, ``w`` [V]): loss_out[i] = inv_wsum * sum_v w_v |posed_iv - target_iv|^2, and into ``grad_out`` [N,V,3] (None:
+    not wanted) its gradient to ``posed``, 2 inv_wsum w_v (posed - target).  Rows from ``n`` on are left as they are."""
+    V = posed.shape[1]
+    _lib.check(_lib.lib.cape_smpl_weighted_l2(_p(posed), 3 * V, _p(target), 3 * V, _p(w), inv_wsum, n, V, _p(loss_out),
+                                              _p(grad_out), 3 * V, _stream()), "cape_smpl_weighted_l2")
 
 
 # ---- smplx-compatible factory (demos.py:22-24, 267-283, 312-326) -------------------------------------------------------------

@@ -121,6 +121,8 @@ SIGNATURES = {
     "cape_condnet_fwd": (C.c_int, [_p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     "cape_condnet_bwd": (C.c_int, [_p, _i32, _p, _i32, _p, _p, _p, _i32, _p, _i32, _p, _p, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _i32, _i32, _p]),
     "cape_gconv_dw_reduce_batch": (C.c_int, [C.c_void_p, _i32, _p]),
+    "cape_gconv_dw_batch": (C.c_int, [C.c_void_p, _i32, _p]),
+    "cape_gconv_dw_batch_plan": (C.c_int, [C.c_void_p, _i32, C.POINTER(_i32), _i32, C.POINTER(_i32)]),
     "cape_gconv_dw_plan": (C.c_int, [_SRCP, _i32, _p, _i64, _i32, _p, C.c_uint32, _i32, _i32, _i32, C.POINTER(_i32)]),
     "cape_gconv_fwd_bf16": (C.c_int, [_SRCP, _i32, _p, _i64, _i32, _i32, _i32, _i32, _p, _i32, _i32, _p,
                                       C.POINTER(CapeRank), _i32, _p]),

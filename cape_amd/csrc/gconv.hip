@@ -17,6 +17,8 @@
 #include "gemm_h2.h"
 #include "narrow.h"
 #include <stdlib.h>
+#include <algorithm>
+#include <vector>
 
 namespace {
 
@@ -1062,12 +1064,18 @@ int gconv_dw_plan_impl(const cape_src_t *srcs, int32_t nsrc, const float *dz, in
     return CAPE_OK;
 }
 struct DwReduceParams;
+// what a launch would run, without running it (cape_gconv_dw_batch): its parameters, its per-layer plan, its kernel
+struct DwDescribe {
+    DwParams p;
+    DwPlan pl;
+    bool use_h2, v4;
+};
 int gconv_dw_stage_impl(const cape_src_t *srcs, int32_t nsrc, const float *dz,
                         int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
                         int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
                         int64_t workspace_bytes, int32_t stage, void *stream, bool bf16,
                         DwReduceParams *batch_rp = nullptr, int *batch_vec = nullptr, int *batch_blocks = nullptr,
-                        const cape_h2_dw_t *h2 = nullptr);
+                        const cape_h2_dw_t *h2 = nullptr, DwDescribe *describe = nullptr);
 }  // namespace
 
 extern "C" int cape_gconv_dw_plan(const cape_src_t *srcs, int32_t nsrc, const float *dz, int64_t dz_sample_stride,
@@ -1136,7 +1144,7 @@ int gconv_dw_stage_impl(const cape_src_t *srcs, int32_t nsrc, const float *dz,
                         int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
                         int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
                         int64_t workspace_bytes, int32_t stage, void *stream, bool bf16,
-                        DwReduceParams *batch_rp, int *batch_vec, int *batch_blocks, const cape_h2_dw_t *h2) {
+                        DwReduceParams *batch_rp, int *batch_vec, int *batch_blocks, const cape_h2_dw_t *h2, DwDescribe *describe) {
     if (stage < 0 || stage > 3 || (stage == 3 && (!batch_rp || !batch_vec || !batch_blocks))) return CAPE_EINVAL;
     if (!srcs || nsrc < 1 || nsrc > CAPE_MAX_SRC || !dz || N < 1 || Mo < 1 || F < 1 || lddz < F || !workspace)
         return CAPE_EINVAL;
@@ -1176,6 +1184,13 @@ int gconv_dw_stage_impl(const cape_src_t *srcs, int32_t nsrc, const float *dz,
     p.ngroups = pl.ngroups; p.samples_per_group = pl.samples_per_group;
     p.ws = (float *)workspace; p.slab = pl.slab;
     fill_h2_dw(p, bf16 ? nullptr : h2);
+    if (describe) {
+        describe->p = p;
+        describe->pl = pl;
+        describe->use_h2 = use_h2;
+        describe->v4 = use_h2 && h2_dw_v4(p, pl.ct, pl.ft);
+        return CAPE_OK;
+    }
     hipStream_t st = (hipStream_t)stream;
     dim3 grid((unsigned)(pl.ntiles * ((pl.ngroups * pl.rsplit + 7) / 8) * 8)), block(256);     // cape_map_dw_block
     if (stage >= 2) {
@@ -1272,5 +1287,192 @@ extern "C" int cape_gconv_dw_reduce_batch(const cape_dw_item_t *items, int32_t n
     B.blk_off[nitems] = off;
     CAPE_LAUNCH(dw_reduce_batch_kernel, dim3((unsigned)off), dim3(256), 0, (hipStream_t)stream, B);
     CAPE_LAUNCH_CHECK();
+    return CAPE_OK;
+}
+
+// =============================================================================================================
+// Weight gradients per phase: the contractions of several queued launches of dw_h2_kernel<128, 128, true> as ONE grid
+// (DwBatch, gconv_shared.h).  Every item keeps the contraction splits of its own launch -- the same partial slabs in the same
+// workspace, so the reduction and the gradients are those of the per-layer launches bit for bit -- but the tiles of all items
+// queue for the chip together: one launch's ramp and drain instead of one per layer, the longest workgroups first.  (Cutting
+// the items into FEWER splits for the shared grid was built and measured too: 2.3-2.8 % of the step instead of 1.7 %, but
+// fewer, longer partial sums move the gradients' rounding by 2e-6 of their maximum)  The plan is
+// a pure function of the items' shapes.
+// =============================================================================================================
+namespace {
+struct DwbShape { int N, tiles, nseg, ngroups, rsplit, rows_per_split; };     // the item's own plan
+struct DwbLaunch {
+    int first, n;                                                 // items first .. first + n - 1 of the list
+    int order[DWB_MAX_ITEMS];                                     // table position -> item of the launch: longest workgroups first
+    int rot[DWB_MAX_ITEMS];                                       // (by table position) XCD of split 0
+    int start[8][DWB_MAX_ITEMS + 2];
+    int grid, units;
+};
+
+// splits of an item (rotation rot) that run on XCD x: s = ((x - rot) & 7) + 8 q < count
+inline int dwb_on_xcd(int count, int rot, int x) {
+    const int s0 = (x - rot) & 7;
+    return s0 < count ? (count - 1 - s0) / 8 + 1 : 0;
+}
+
+// One launch: the items' places on the 8 XCDs.
+inline void dwb_plan_launch(const DwbShape *sh, int n, DwbLaunch &L) {
+    long long rows[DWB_MAX_ITEMS];
+    L.units = 0;
+    for (int i = 0; i < n; ++i) {
+        L.order[i] = i;
+        rows[i] = (long long)(sh[i].N / sh[i].ngroups) * sh[i].rows_per_split;
+        L.units += sh[i].tiles * sh[i].ngroups * sh[i].rsplit;
+    }
+    // table order: longest workgroups first (then list order); each item's rotation: the one that leaves the busiest XCD
+    // with the least work (tiles x rows), the lowest on a tie
+    std::stable_sort(L.order, L.order + n, [&](int a, int b) { return rows[a] > rows[b]; });
+    long long load[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    for (int k = 0; k < n; ++k) {
+        const int i = L.order[k], count = sh[i].ngroups * sh[i].rsplit;
+        const long long w = (long long)sh[i].tiles * rows[i];
+        int best = 0;
+        long long best_peak = -1;
+        for (int r = 0; r < 8; ++r) {
+            long long peak = 0;
+            for (int x = 0; x < 8; ++x) {
+                const long long v = load[x] + w * dwb_on_xcd(count, r, x);
+                peak = v > peak ? v : peak;
+            }
+            if (best_peak < 0 || peak < best_peak) { best_peak = peak; best = r; }
+        }
+        L.rot[k] = best;
+        for (int x = 0; x < 8; ++x) load[x] += w * dwb_on_xcd(count, best, x);
+    }
+    int longest = 0;
+    for (int x = 0; x < 8; ++x) {
+        int start = 0;
+        for (int k = 0; k < DWB_MAX_ITEMS + 2; ++k) {
+            L.start[x][k] = start;
+            if (k < n) start += sh[L.order[k]].tiles * dwb_on_xcd(sh[L.order[k]].ngroups * sh[L.order[k]].rsplit, L.rot[k], x);
+        }
+        longest = start > longest ? start : longest;
+    }
+    L.grid = 8 * longest;
+}
+
+// The list cut into launches (in list order: what the argument table holds), each planned on its own.
+inline void dwb_plan(const DwbShape *sh, int n, std::vector<DwbLaunch> &out) {
+    out.clear();
+    int i = 0;
+    while (i < n) {
+        DwbLaunch L;
+        L.first = i;
+        int segs = 0, k = 0;
+        while (i + k < n && k < DWB_MAX_ITEMS && segs + sh[i + k].nseg <= DWB_MAX_SEGS) {
+            segs += sh[i + k].nseg;
+            ++k;
+        }
+        L.n = k;
+        dwb_plan_launch(sh + i, k, L);
+        out.push_back(L);
+        i += k;
+    }
+}
+
+// an item of the list: does it run dw_h2_kernel<128, 128, true>, and with which tiles and splits?
+inline int dwb_describe(const cape_dw_item_t &t, DwDescribe &d, DwbShape &s) {
+    if (t.bf16 || !t.h2) return CAPE_EINVAL;
+    const int rc = gconv_dw_stage_impl(t.srcs, t.nsrc, (const float *)t.dz, t.dz_sample_stride, t.lddz, (const float *)t.dz2,
+                                       t.dz2_mask, t.N, t.Mo, t.F, t.accumulate, t.workspace, t.workspace_bytes, 1, nullptr,
+                                       false, nullptr, nullptr, nullptr, t.h2, &d);
+    if (rc) return rc;
+    if (!d.use_h2 || !d.v4 || t.nsrc > DWB_MAX_SEGS) return CAPE_EINVAL;
+    s.N = t.N; s.nseg = t.nsrc;
+    s.tiles = d.pl.ntiles;
+    s.ngroups = d.pl.ngroups; s.rsplit = d.pl.rsplit; s.rows_per_split = d.pl.rows_per_split;
+    return CAPE_OK;
+}
+
+int dwb_prepare(const cape_dw_item_t *items, int nitems, std::vector<DwDescribe> &desc, std::vector<DwbShape> &sh,
+                std::vector<DwbLaunch> &launches) {
+    if (!items || nitems < 1 || nitems > CAPE_MAX_DW_REDUCE_ITEMS) return CAPE_EINVAL;
+    desc.resize(nitems);
+    sh.resize(nitems);
+    for (int i = 0; i < nitems; ++i) {
+        const int rc = dwb_describe(items[i], desc[i], sh[i]);
+        if (rc) return rc;
+    }
+    dwb_plan(sh.data(), nitems, launches);
+    return CAPE_OK;
+}
+}  // namespace
+
+extern "C" int cape_gconv_dw_batch_plan(const cape_dw_item_t *items, int32_t nitems, int32_t *units, int32_t max_units, int32_t info[4]) {
+    std::vector<DwDescribe> desc;
+    std::vector<DwbShape> sh;
+    std::vector<DwbLaunch> launches;
+    const int rc = dwb_prepare(items, nitems, desc, sh, launches);
+    if (rc) return rc;
+    if (!info) return CAPE_EINVAL;
+    int nunits = 0, grid = 0;
+    for (size_t l = 0; l < launches.size(); ++l) {
+        const DwbLaunch &L = launches[l];
+        grid = L.grid > grid ? L.grid : grid;
+        // the workgroups as the kernel decodes them: XCD x, the items in table order, an item's splits on x, a split's tiles
+        for (int x = 0; x < 8; ++x)
+            for (int tk = 0; tk < L.n; ++tk) {
+                const int k = L.order[tk];
+                const DwDescribe &d = desc[L.first + k];
+                const DwbShape &c = sh[L.first + k];
+                const int spg = c.N / c.ngroups;
+                for (int j = L.start[x][tk]; j < L.start[x][tk + 1]; ++j, ++nunits) {
+                    if (!units || nunits >= max_units) continue;
+                    const int q = (j - L.start[x][tk]) / c.tiles, t = (j - L.start[x][tk]) % c.tiles;
+                    const int split = ((x - L.rot[tk]) & 7) + 8 * q;
+                    int si = 0;
+                    while (si + 1 < d.p.nsrc && t >= d.p.tile_off[si + 1]) ++si;
+                    const int grp = split / c.rsplit, rs = split % c.rsplit;
+                    const int wra = rs * c.rows_per_split, rb = wra + c.rows_per_split < d.p.Mo ? wra + c.rows_per_split : d.p.Mo;
+                    int32_t *u = units + 10 * (size_t)nunits;
+                    u[0] = (int32_t)l; u[1] = 8 * j + x; u[2] = L.first + k; u[3] = si; u[4] = t - d.p.tile_off[si];
+                    u[5] = split; u[6] = grp * spg; u[7] = grp * spg + spg; u[8] = wra; u[9] = rb;
+                }
+            }
+    }
+    info[0] = (int32_t)launches.size(); info[1] = nunits; info[2] = (int32_t)sizeof(DwParams); info[3] = grid;
+    return CAPE_OK;
+}
+
+extern "C" int cape_gconv_dw_batch(const cape_dw_item_t *items, int32_t nitems, void *stream) {
+    std::vector<DwDescribe> desc;
+    std::vector<DwbShape> sh;
+    std::vector<DwbLaunch> launches;
+    const int rc = dwb_prepare(items, nitems, desc, sh, launches);
+    if (rc) return rc;
+    for (const DwbLaunch &L : launches) {
+        DwParams P = DwParams();
+        DwBatch &B = P.bt;
+        int seg = 0;
+        for (int tk = 0; tk < L.n; ++tk) {                        // (table order)
+            const int k = L.order[tk];
+            const DwParams &p = desc[L.first + k].p;
+            DwBatchItem &it = B.item[tk];
+            it.dz = p.dz; it.dzrm = p.dzrm; it.dz2 = p.dz2; it.dz2rm = p.dz2rm; it.dzs = p.dzs;
+            it.ws = p.ws; it.slab = p.slab;
+            it.lddz = p.lddz; it.dzrmw = p.dzrmw; it.dz2rmw = p.dz2rmw; it.F = p.F; it.N = p.N; it.Mo = p.Mo; it.ftiles = p.ftiles;
+            it.rsplit = p.rsplit; it.rows_per_split = p.rows_per_split; it.samples_per_group = p.samples_per_group;
+            it.seg0 = seg; it.nseg = p.nsrc;
+            it.ntiles = sh[L.first + k].tiles; it.rot = L.rot[tk];
+            for (int s = 0; s < p.nsrc; ++s, ++seg) {
+                DwBatchSeg &sg = B.seg[seg];
+                sg.x = p.s[s].x; sg.rm = p.s[s].rm; sg.xs = p.s[s].xs; sg.part_off = p.part_off[s];
+                sg.ldx = p.s[s].ldx; sg.C = p.s[s].C;
+                sg.rmw_use2 = p.s[s].rmw | (int)((p.dz2_mask >> s) & 1u) << 16;
+                sg.tile_off = p.tile_off[s];
+            }
+        }
+        B.nseg = seg;
+        for (int x = 0; x < 8; ++x)
+            for (int g = 0; g < DWB_MAX_ITEMS + 2; ++g) B.start[x][g] = L.start[x][g];
+        if (L.grid < 8) return CAPE_EINVAL;
+        CAPE_LAUNCH((dw_h2_kernel<128, 128, true>), dim3((unsigned)L.grid), dim3(256 * H2_DW_KG), 0, (hipStream_t)stream, P);
+        CAPE_LAUNCH_CHECK();
+    }
     return CAPE_OK;
 }

@@ -96,6 +96,41 @@ __device__ __forceinline__ void h2_store_rowmax(const GconvParams &p, int n, int
     }
 }
 
+// Batch mode of dw_h2_kernel (cape_gconv_dw_batch): the contractions of SEVERAL queued launches ("items") in one grid.  The
+// table travels in the kernel arguments.  A GROUP is one contraction split of one item: all its tiles read the same rows of
+// the item's operands, so a group runs on ONE XCD (block b -> XCD b & 7, see cape_map_dw_block).  Split s of item k runs on
+// XCD (s + rot_k) & 7; on XCD x the items follow each other in table order (longest workgroups first), item k from workgroup
+// start[x][k] on (block 8 j + x is workgroup j of XCD x): workgroup start + q * ntiles + t is tile t of the q-th of the
+// item's splits on that XCD.  How many splits an item is cut into, and its rotation, is decided by dwb_plan (gconv.hip).
+constexpr int DWB_MAX_ITEMS = 6, DWB_MAX_SEGS = 12;
+struct DwBatchItem {
+    const float *dz, *dzrm;            // gradient operand and its row bounds ...
+    const float *dz2, *dz2rm;          // ... second gradient operand (segments with use2)
+    long long dzs;
+    float *ws;                         // partial slabs of this item
+    long long slab;
+    int lddz, dzrmw, dz2rmw, F, N, Mo, ftiles;
+    int rsplit, rows_per_split, samples_per_group;
+    int seg0, nseg;                    // the item's sources: segments seg0 .. seg0 + nseg - 1
+    int ntiles, rot;                   // tiles of all sources; XCD of split 0
+};
+struct DwBatchSeg {
+    const float *x, *rm;
+    long long xs;
+    long long part_off;                // element offset of this source inside one partial slab
+    int ldx, C;
+    int rmw_use2;                      // rmw | use2 << 16
+    int tile_off;                      // first tile of this source among the item's tiles
+};
+struct DwBatch {
+    DwBatchItem item[DWB_MAX_ITEMS];
+    DwBatchSeg seg[DWB_MAX_SEGS];
+    int start[8][DWB_MAX_ITEMS + 2];   // per XCD: first workgroup of each item, non-decreasing; entries from the item count on
+                                       // = the length of the XCD's list
+    int nseg = 0;                      // 0: an ordinary launch
+    int pad_;
+};
+
 // Weight-gradient launch: each workgroup owns one [CT x FT] tile of one source's dW and one (sample group,
 // row range) slice of the contraction; partials go to a workspace slab per split.
 struct DwParams {
@@ -121,7 +156,9 @@ struct DwParams {
     // sources are packed back to back when they share dz (small layers: one tile holds several sources), otherwise
     // each source starts on a tile boundary.  vstart[nsrc] = length of the axis.
     int vstart[CAPE_MAX_SRC + 1];
+    DwBatch bt;                        // dw_h2_kernel only: bt.nseg > 0 = batch mode, everything above is unused
 };
+static_assert(sizeof(DwParams) <= 3584, "kernel arguments: 4 KB including the hidden ones");
 
 // Epilogue of one workgroup tile: rank-1 condition terms, bias + activation (or, in DUAL mode,
 // relu(acc) + acc2 with the ReLU sign bitmask), store.  Accumulator layout of the 32x32 MFMA:

@@ -392,6 +392,11 @@ constexpr int H2_DW_KG = 2;
 // in consecutive 64-byte rows every store of a wave would fall on four 16-byte slots) the rows of a quad are ROTATED by
 // (quad >> 2) & 3 inside the stage; the accumulator rows / columns come out in the same rotated order and the slab store
 // undoes it.  CAPE_DW_V4=0 keeps the 4-byte form (A/B).
+// Batch mode (round 7, p.bt.nseg > 0): the grid holds the tiles of SEVERAL queued launches (DwBatch, gconv_shared.h;
+// cape_gconv_dw_batch); a workgroup looks up its item, source, tile and split in the argument table and then runs the same
+// pipeline on that item's operands.  Nothing below the look-up knows the difference.  Only the <128, 128, true> instantiation
+// has the mode (the others are never launched batched and keep the per-layer look-up alone).  (Two instantiations of the whole
+// body behind one branch were tried and dropped: 253 VGPRs, 20 bytes of scratch per lane.)
 template <int CT, int FT, bool V4 = true>
 __global__ __launch_bounds__(256 * H2_DW_KG, 1) void dw_h2_kernel(DwParams p) {
     constexpr int RK = 32, KG = H2_DW_KG;
@@ -414,42 +419,93 @@ __global__ __launch_bounds__(256 * H2_DW_KG, 1) void dw_h2_kernel(DwParams p) {
     const int rg = tid >> 6;
     const int ca = tid & 63, fb = tid & 63;
 
-    const int ntiles = p.tile_off[p.nsrc];
-    int tile, split;
-    if (!cape_map_dw_block(blockIdx.x, ntiles, p.ngroups * p.rsplit, tile, split)) return;
-    const int grp = split / p.rsplit;
-    const int rs = split % p.rsplit;
-    const int n_begin = grp * p.samples_per_group;
-    const int n_end = min(p.N, n_begin + p.samples_per_group);
-    int si = 0;
-    while (si + 1 < p.nsrc && tile >= p.tile_off[si + 1]) ++si;
-    // (the source is indexed at run time: its fields are read through the kernel-argument segment -- scalar loads with a register
-    // offset -- and copied; a reference into the by-value parameter can make hipcc copy the whole block to scratch memory)
-    typedef const __attribute__((address_space(4))) SrcDev *SrcTab;
-    const SrcTab src_tab = (SrcTab)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(DwParams, s));
+    // ---- this workgroup's work: one tile of one source's gradient block, one (sample group, row range) of the contraction.
+    //      W = the launch's description of it, from the per-layer fields of p or (batch mode) from the item / segment table.
+    //      (A table is indexed at run time: its fields are read through the kernel-argument segment -- scalar loads with a
+    //      register offset -- and copied; a reference into the by-value parameter can make hipcc copy the whole block to
+    //      scratch memory.)
+    typedef const __attribute__((address_space(4))) char *KArg;
+    const KArg karg = (KArg)__builtin_amdgcn_kernarg_segment_ptr();
     struct { const float *x, *rm; long long xs; int ldx, C, rmw; } S;
-    S.x = src_tab[si].x; S.rm = src_tab[si].rm; S.xs = src_tab[si].xs; S.ldx = src_tab[si].ldx; S.C = src_tab[si].C; S.rmw = src_tab[si].rmw;
-    const int lt = tile - p.tile_off[si];
-    const int c0 = (lt / p.ftiles) * CT;
-    const int f0 = (lt % p.ftiles) * FT;
-    const int wra = rs * p.rows_per_split;                        // the WORKGROUP's row range ...
-    const int rb = min(p.Mo, wra + p.rows_per_split);
+    struct { const float *dz, *rmz; float *out; long long dzs; int wz, lddz, F, N, Mo, ftiles, rsplit, rows_per_split, samples_per_group; } W;
+    int lt, split;
+    constexpr bool CAN_BATCH = CT == 128 && FT == 128 && V4;
+    if (CAN_BATCH && p.bt.nseg > 0) {
+        // batch mode (DwBatch): the item of this block in its XCD's list -- one row of the table, compared entry by entry with
+        // constant indices --, then the split and the tile, then the source that owns the tile
+        const int xcd = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
+        typedef const __attribute__((address_space(4))) int *StartTab;
+        typedef const __attribute__((address_space(4))) DwBatchSeg *SegTab;
+        typedef const __attribute__((address_space(4))) DwBatchItem *ItemTab;
+        const StartTab st = (StartTab)(karg + offsetof(DwParams, bt) + offsetof(DwBatch, start)) + xcd * (DWB_MAX_ITEMS + 2);
+        const SegTab sgt = (SegTab)(karg + offsetof(DwParams, bt) + offsetof(DwBatch, seg));
+        const ItemTab itt = (ItemTab)(karg + offsetof(DwParams, bt) + offsetof(DwBatch, item));
+        int ii = 0, j0 = st[0];
+#pragma unroll
+        for (int i = 1; i < DWB_MAX_ITEMS; ++i) {
+            const int o = st[i];
+            if (j >= o) { ii = i; j0 = o; }
+        }
+        if (j >= st[DWB_MAX_ITEMS]) return;                        // past the end of this XCD's list
+        const int ntl = itt[ii].ntiles;
+        const int q = (j - j0) / ntl;
+        const int tile = (j - j0) - q * ntl;
+        split = ((xcd - itt[ii].rot) & 7) + 8 * q;
+        int sg = itt[ii].seg0;
+        const int sg_end = sg + itt[ii].nseg;
+        while (sg + 1 < sg_end && tile >= sgt[sg + 1].tile_off) ++sg;
+        lt = tile - sgt[sg].tile_off;
+        S.x = sgt[sg].x; S.rm = sgt[sg].rm; S.xs = sgt[sg].xs; S.ldx = sgt[sg].ldx; S.C = sgt[sg].C;
+        const int ru = sgt[sg].rmw_use2;
+        S.rmw = ru & 0xFFFF;
+        const bool two = (ru >> 16) != 0;
+        W.dz = two ? itt[ii].dz2 : itt[ii].dz;
+        W.rmz = two ? itt[ii].dz2rm : itt[ii].dzrm;
+        W.wz = two ? itt[ii].dz2rmw : itt[ii].dzrmw;
+        W.dzs = itt[ii].dzs; W.lddz = itt[ii].lddz; W.F = itt[ii].F; W.N = itt[ii].N; W.Mo = itt[ii].Mo; W.ftiles = itt[ii].ftiles;
+        W.rsplit = itt[ii].rsplit; W.rows_per_split = itt[ii].rows_per_split; W.samples_per_group = itt[ii].samples_per_group;
+        W.out = itt[ii].ws + (long long)split * itt[ii].slab + sgt[sg].part_off;
+    } else {
+        const int ntiles = p.tile_off[p.nsrc];
+        int tile;
+        if (!cape_map_dw_block(blockIdx.x, ntiles, p.ngroups * p.rsplit, tile, split)) return;
+        int si = 0;
+        while (si + 1 < p.nsrc && tile >= p.tile_off[si + 1]) ++si;
+        typedef const __attribute__((address_space(4))) SrcDev *SrcTab;
+        const SrcTab src_tab = (SrcTab)(karg + offsetof(DwParams, s));
+        S.x = src_tab[si].x; S.rm = src_tab[si].rm; S.xs = src_tab[si].xs; S.ldx = src_tab[si].ldx; S.C = src_tab[si].C; S.rmw = src_tab[si].rmw;
+        lt = tile - p.tile_off[si];
+        const bool two = ((p.dz2_mask >> si) & 1u) != 0;
+        W.dz = two ? p.dz2 : p.dz;
+        W.rmz = two ? p.dz2rm : p.dzrm;
+        W.wz = two ? p.dz2rmw : p.dzrmw;
+        W.dzs = p.dzs; W.lddz = p.lddz; W.F = p.F; W.N = p.N; W.Mo = p.Mo; W.ftiles = p.ftiles;
+        W.rsplit = p.rsplit; W.rows_per_split = p.rows_per_split; W.samples_per_group = p.samples_per_group;
+        W.out = p.ws + (long long)split * p.slab + p.part_off[si];
+    }
+    const int grp = split / W.rsplit;
+    const int rs = split % W.rsplit;
+    const int n_begin = grp * W.samples_per_group;
+    const int n_end = min(W.N, n_begin + W.samples_per_group);
+    const int c0 = (lt / W.ftiles) * CT;
+    const int f0 = (lt % W.ftiles) * FT;
+    const int wra = rs * W.rows_per_split;                        // the WORKGROUP's row range ...
+    const int rb = min(W.Mo, wra + W.rows_per_split);
     // ... and this group's part of it: whole chunks, the same number for every group (a part that reaches past rb reads zeros
     // there -- the buffer resources end at row rb -- so the groups run the same trip count and share their barriers)
     const int chunks = ((rb - wra + RK - 1) / RK + KG - 1) / KG;
     const int ra = wra + kg * chunks * RK;
-    const bool two = ((p.dz2_mask >> si) & 1u) != 0;
-    const float *dz0 = two ? p.dz2 : p.dz;
+    const float *dz0 = W.dz;
 
     // ---- scales of the workgroup's range (one pair for both groups: their accumulators are added unscaled)
     float sx, sz, inv;
     {
-        const float *rmz = two ? p.dz2rm : p.dzrm;
-        const int wz = two ? p.dz2rmw : p.dzrmw;
+        const float *rmz = W.rmz;
+        const int wz = W.wz;
         float mx = 0.f, mz = 0.f;
         for (int n = n_begin; n < n_end; ++n) {
-            const float *px = S.rm + ((long long)n * p.Mo + wra) * S.rmw;
-            const float *pz = rmz + ((long long)n * p.Mo + wra) * wz;
+            const float *px = S.rm + ((long long)n * W.Mo + wra) * S.rmw;
+            const float *pz = rmz + ((long long)n * W.Mo + wra) * wz;
             // (row widths are multiples of 4 and the arrays 16-byte aligned: float4 loads, four in flight per thread)
             const float4 *px4 = reinterpret_cast<const float4 *>(px), *pz4 = reinterpret_cast<const float4 *>(pz);
             const int nx = (rb - wra) * (S.rmw >> 2), nz = (rb - wra) * (wz >> 2);
@@ -508,19 +564,19 @@ __global__ __launch_bounds__(256 * H2_DW_KG, 1) void dw_h2_kernel(DwParams p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         xoff[j] = ((8 * rg + j) * S.ldx + c0 + ca) * 4;
-        zoff[j] = ((8 * rg + j) * p.lddz + f0 + fb) * 4;
+        zoff[j] = ((8 * rg + j) * W.lddz + f0 + fb) * 4;
     }
     __amdgpu_buffer_rsrc_t rx, rz;
     auto open_sample = [&]() {
         // (bounded at the last row's last channel, not at the end of its padded pitch: the overhang of an edge tile reads 0)
         rx = __builtin_amdgcn_make_buffer_rsrc((void *)(S.x + (long long)l_n * S.xs), 0, ((rb - 1) * S.ldx + S.C) * 4, 0x00020000);
-        rz = __builtin_amdgcn_make_buffer_rsrc((void *)(dz0 + (long long)l_n * p.dzs), 0, ((rb - 1) * p.lddz + p.F) * 4, 0x00020000);
+        rz = __builtin_amdgcn_make_buffer_rsrc((void *)(dz0 + (long long)l_n * W.dzs), 0, ((rb - 1) * W.lddz + W.F) * 4, 0x00020000);
     };
     // (the row advance goes into the per-lane offset, which IS range-checked; a scalar offset operand would not be)
     // (operand-dependent values are chosen by masks on VALUES: a select between two kernel-argument addresses makes hipcc copy
     // the whole parameter block to scratch memory)
     const int mb = -(int)is_b;
-    const int ld_x = S.ldx, ld_z = p.lddz;
+    const int ld_x = S.ldx, ld_z = W.lddz;
     if constexpr (V4) voff4 = ((((rgi * RPB) * ld_z + f0 + 4 * cq) * 4) & mb) | ((((rgi * RPA) * ld_x + c0 + 4 * cq) * 4) & ~mb);
     auto load4 = [&]() __attribute__((always_inline)) {      // ... and advances the chunk cursor
         auto ld = [&](__amdgpu_buffer_rsrc_t rs, int base, int pitch, int j) __attribute__((always_inline)) {
@@ -552,7 +608,7 @@ __global__ __launch_bounds__(256 * H2_DW_KG, 1) void dw_h2_kernel(DwParams p) {
                 xa[ch][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rx, xoff[j] + bx + 256 * ch, 0, 0));
     };
     auto load_b = [&]() {                            // ... and advances the chunk cursor: call after load_a
-        const int bz = l_r * p.lddz * 4;
+        const int bz = l_r * W.lddz * 4;
 #pragma unroll
         for (int j = 0; j < 8; ++j)
 #pragma unroll
@@ -772,7 +828,7 @@ __global__ __launch_bounds__(256 * H2_DW_KG, 1) void dw_h2_kernel(DwParams p) {
 #pragma unroll
                 for (int g = 0; g < 16; ++g) acc[a][b][g] += park[((a * TN + b) * 16 + g) * 256 + tid];
     }
-    float *out = p.ws + (long long)split * p.slab + p.part_off[si];
+    float *out = W.out;
     // V4: stage row R holds channel 4 q + ((R & 3) - (q >> 2) & 3), q = R >> 2 (accumulator rows and columns alike)
     auto unrot = [](int R) { return V4 ? (R & ~3) | (((R & 3) - (R >> 4)) & 3) : R; };
 #pragma unroll
@@ -783,7 +839,7 @@ __global__ __launch_bounds__(256 * H2_DW_KG, 1) void dw_h2_kernel(DwParams p) {
 #pragma unroll
             for (int g = 0; g < 16; ++g) {
                 const int c = c0 + unrot(wm * WTM + a * 32 + (g & 3) + 8 * (g >> 2) + 4 * lh);
-                if (c < S.C && f < p.F) out[(long long)c * p.F + f] = acc[a][b][g] * inv;
+                if (c < S.C && f < W.F) out[(long long)c * W.F + f] = acc[a][b][g] * inv;
             }
         }
 }
@@ -845,17 +901,22 @@ inline bool h2_dw_eligible(const DwParams &p) {
     return true;
 }
 
-inline void h2_dw_launch(const DwParams &p, int ct, int ft, dim3 grid, hipStream_t st) {
-    const dim3 block(256 * H2_DW_KG);
+// does a launch on ct x ft tiles take the 16-byte-load instantiation dw_h2_kernel<128, 128, true>?  (Every operand with 16-byte
+// aligned rows.)  Also the condition for joining a batched launch (cape_gconv_dw_batch).
+inline bool h2_dw_v4(const DwParams &p, int ct, int ft) {
     static const int v4 = getenv("CAPE_DW_V4") ? atoi(getenv("CAPE_DW_V4")) : 1;
-    // (16-byte loads: every operand with 16-byte aligned rows)
-    bool ok = v4 && (p.lddz & 3) == 0 && (p.dzs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.dz) & 15) == 0 &&
+    bool ok = v4 && ct == 128 && ft == 128 && (p.lddz & 3) == 0 && (p.dzs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.dz) & 15) == 0 &&
               (!p.dz2 || (reinterpret_cast<uintptr_t>(p.dz2) & 15) == 0);
     for (int i = 0; i < p.nsrc && ok; ++i)
         ok = (p.s[i].ldx & 3) == 0 && (p.s[i].xs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.s[i].x) & 15) == 0;
+    return ok;
+}
+
+inline void h2_dw_launch(const DwParams &p, int ct, int ft, dim3 grid, hipStream_t st) {
+    const dim3 block(256 * H2_DW_KG);
     // (128 x 128 tiles only: with a 64-wide operand the two wave pairs of a group get unequal shares -- measured 12.8 -> 18.4 us on
     // 128 x 64, 17.3 -> 26.2 on 64 x 128 -- and 64 x 64 gains nothing; 128 x 128: 64.1 -> 62.6, 37.1 -> 36.3, 34.3 -> 33.6 us)
-    if (ok && ct == 128 && ft == 128) {
+    if (h2_dw_v4(p, ct, ft)) {
         CAPE_LAUNCH((dw_h2_kernel<128, 128, true>), grid, block, 0, st, p);
         return;
     }

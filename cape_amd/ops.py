@@ -390,6 +390,10 @@ FUSE_ACT_GRAD = int(_os.environ.get("CAPE_FUSE_ACT_GRAD", "1"))
 # FUSE_PREP_SPMM = 0: the affine blocks at one resolution run cape_bwd_prep and cape_spmm instead of cape_bwd_prep_spmm (the A/B form)
 FUSE_PREP_SPMM = int(_os.environ.get("CAPE_FUSE_PREP_SPMM", "1"))
 DW_V4 = int(_os.environ.get("CAPE_DW_V4", "1"))        # mirror of the library's switch (csrc/gemm_h2.h h2_dw_launch): kernel NAMES only
+# weight gradients per phase: deferred launches of dw_h2_kernel<128, 128, true> run their contractions at the flush as ONE grid
+# (cape_gconv_dw_batch; every layer keeps its own splits, so the gradients are bit for bit the same); 0: every launch contracts
+# when it is queued (A/B)
+DW_BATCH = int(_os.environ.get("CAPE_DW_BATCH", "1"))
 _CHAIN = [False]
 
 
@@ -740,7 +744,6 @@ def gconv_dw(entries, dz, accumulate=False, dz2=None, defer=False):
             plan = (C.c_int32 * 4)()
             dw_plan(plan)
             PLAN_LOG.add(("dw", plan[0], plan[1], plan[2]) + (("bf16",) if bf else ()))
-        dw_stage(1)
         it = _lib.CapeDwItem()
         it.srcs, it.nsrc = C.addressof(arr), len(entries)
         it.dz, it.dz_sample_stride, it.lddz = p.value, ss, ld
@@ -748,7 +751,16 @@ def gconv_dw(entries, dz, accumulate=False, dz2=None, defer=False):
         it.N, it.Mo, it.F, it.accumulate, it.bf16 = N, Mo, F, 1 if accumulate else 0, 1 if bf else 0
         it.workspace, it.workspace_bytes = ws.data_ptr(), need
         it.h2 = C.addressof(h2) if h2 is not None else None        # (the reduction counts the slabs the two-piece kernel wrote)
-        DEFERRED_DW.append((it, arr, ws, dz, dz2, [e["x"] for e in entries], h2))   # keep every buffer alive until the flush
+        # weight gradients per phase: a launch of dw_h2_kernel<128, 128, true> leaves its CONTRACTION to the flush as well, where
+        # all queued ones of the sweep run as one grid (the library says which launches qualify)
+        batch = bool(DW_BATCH) and h2 is not None and \
+            lib.cape_gconv_dw_batch_plan(C.addressof(it), 1, None, 0, (C.c_int32 * 4)()) == 0
+        if not batch:
+            dw_stage(1)
+        # the operands of a batched item are read at the flush: remember their versions (tensors AND row bounds)
+        held = [dz] + ([dz2] if dz2 is not None else []) + [e["x"] for e in entries] + (list(h2._keep) if batch else [])
+        vers = [t._version for t in held] if batch else None
+        DEFERRED_DW.append((it, arr, ws, held, h2, batch, vers))   # keep every buffer alive until the flush
         return
     if LAUNCH_LOG is None and PLAN_LOG is None:
         launch()
@@ -1011,10 +1023,22 @@ DEFERRED_DW = []          # queued weight-gradient slab reductions (gconv_dw(def
 DEFERRED_GN = []          # queued batch sums of group-norm parameter-gradient partials (GroupNormFn.backward), likewise
 
 def _flush_dw():
-    """The queued fixed-order slab reductions of the weight gradient, as batched launches."""
+    """The queued weight-gradient work: the contractions that were left to the flush as one grid (cape_gconv_dw_batch), then
+    the fixed-order slab reductions of every queued launch, as batched launches in queue order."""
     if DEFERRED_DW:
         queued, DEFERRED_DW[:] = list(DEFERRED_DW), []
         nmax = 12                                    # CAPE_MAX_DW_REDUCE_ITEMS
+        bat = [i for i, q in enumerate(queued) if q[5]]
+        for i in bat:
+            held, vers = queued[i][3], queued[i][6]
+            if any(t._version != v for t, v in zip(held, vers)):
+                raise RuntimeError("an operand of a deferred weight gradient (dz, dz2, a source or its row bounds) was written in "
+                                   "place between gconv_dw(defer=True) and flush_deferred(): the batched contraction reads it at "
+                                   "the flush (CAPE_DW_BATCH=0 contracts at once)")
+        for i0 in range(0, len(bat), nmax):
+            idx = bat[i0:i0 + nmax]
+            arr = (_lib.CapeDwItem * len(idx))(*[queued[i][0] for i in idx])
+            check(lib.cape_gconv_dw_batch(C.addressof(arr), len(idx), _stream()), "cape_gconv_dw_batch")
         for i0 in range(0, len(queued), nmax):
             chunk = queued[i0:i0 + nmax]
             arr = (_lib.CapeDwItem * len(chunk))(*[q[0] for q in chunk])

@@ -340,6 +340,20 @@ typedef struct cape_dw_item {
 } cape_dw_item_t;
 int cape_gconv_dw_reduce_batch(const cape_dw_item_t *items, int32_t nitems, void *stream);
 
+/* Weight gradients per phase: the CONTRACTIONS (stage 1) of up to CAPE_MAX_DW_REDUCE_ITEMS queued items in one launch of
+ * dw_h2_kernel<128, 128, true> (more than one when the list does not fit the kernel's argument table).  Every item must be one
+ * that cape_gconv_dw_stage_h2 would run with that kernel (plan family 4 on 128 x 128 tiles, 16-byte aligned operand rows);
+ * CAPE_EINVAL otherwise.  Every item keeps the contraction splits of its own launch: the workspaces receive the partial slabs
+ * that the stage-1 calls would have written, bit for bit, and cape_gconv_dw_reduce_batch (or stage 2) finishes them as before.
+ * What changes is that the tiles of all items share one grid.
+ * The operands are read when this runs, not when the items were queued: the caller keeps them unchanged until then. */
+int cape_gconv_dw_batch(const cape_dw_item_t *items, int32_t nitems, void *stream);
+/* The plan of cape_gconv_dw_batch for the same arguments (pure query, no launch; a function of the items' shapes alone).
+ * units (may be NULL): up to max_units rows of 10 values, one per workgroup that does work --
+ * {launch, block, item, source, tile of the source, slab, first sample, end sample, first row, end row}.
+ * info = {launches, workgroups in all, bytes of kernel arguments per launch, largest grid}. */
+int cape_gconv_dw_batch_plan(const cape_dw_item_t *items, int32_t nitems, int32_t *units, int32_t max_units, int32_t info[4]);
+
 /* Which kernel cape_gconv_dw would run for these arguments (pure query, no launch): plan[0] = family (0: gather form
  * gconv_dw_kernel, 1: dw_plain_kernel on the exact-fp32 MFMA, 2: dw_packed_kernel, 3: dw_split_kernel on the bf16 pipe
  * with the exact three-way operand split), plan[1], plan[2] = tile channels x output columns, plan[3] = number of

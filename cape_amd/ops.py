@@ -41,7 +41,7 @@ def merged_d_pass(batch):
         return 2 * int(batch) <= 32
     return bool(int(MERGED_D_PASS))
 # sparse operators with at most 12 entries per row are handed to the streaming kernels in ELL form (no row pointer in
-# the dependent-load chain, csrc/elementwise.hip cape_gather_row_ell); 0 = always CSR (the A/B reference, same sums bit for bit)
+# the dependent-load chain, csrc/sparse.hip cape_gather_ell); 0 = always CSR (the A/B reference, same sums bit for bit)
 SPMM_ELL = int(_os.environ.get("CAPE_SPMM_ELL", "1"))
 
 _ACT_OF = {"b1leakyrelu": ("leaky", _lib.BIAS_CHANNEL), "b1relu": ("relu", _lib.BIAS_CHANNEL),
@@ -101,7 +101,7 @@ def _v(t):
 
 
 def _vec_ok(*views):
-    """The condition under which the streaming sparse kernels take their vector form (csrc/elementwise.hip aligned4): four
+    """The condition under which the streaming sparse kernels take their vector form (csrc/views.h aligned4): four
     consecutive elements of every row addressable as one access.  Only that form reads ELL operands."""
     for t in views:
         if t is None:
@@ -121,7 +121,7 @@ def _ptr(t, offset_elems=0):
 def ell_arrays(host):
     """ELL form of a host CSR operator for the streaming sparse kernels: width 4 / 8 / 12, entries in CSR order packed to the
     front, the slots past a row's end = (column of slot 0, 0.0) -- an empty row gets column 0.  Returns (cols, vals) or None.
-    The kernel (csrc/elementwise.hip cape_gather_row_ell) stops at the first group of four whose values are all zero, so an
+    The kernel (csrc/sparse.hip cape_gather_ell) stops at the first group of four whose values are all zero, so an
     operator with a stored all-zero group IN FRONT of a non-zero one (explicit zeros, cancellation in a precomposed chain)
     would lose entries: such operators keep the CSR form."""
     if not (1 <= host.max_row <= 12):
@@ -383,7 +383,7 @@ def dw_kernel_name(fam, ct, ft, bf16=False):
 # consumer (the model's plain encoder stack, reference lib/models.py:541-545: x = cnp(x) in a loop).  Its backward then hands
 # the layer below dz = dx * act'(x) instead of dx (the derivative of that layer's own fused bias + (leaky-)ReLU epilogue, taken
 # from the sign of x) together with the bias-gradient partial sums, all from the epilogue of the summed operator application
-# that produces dx (csrc/elementwise.hip spmm_multi_kernel, SpmmActGrad) -- and that layer skips its backward-prep launch.
+# that produces dx (csrc/sparse.hip spmm_multi_kernel, SpmmActGrad) -- and that layer skips its backward-prep launch.
 # FUSE_ACT_GRAD = 0 keeps the op-by-op form (the A/B reference).
 # --------------------------------------------------------------------------------------------
 FUSE_ACT_GRAD = int(_os.environ.get("CAPE_FUSE_ACT_GRAD", "1"))
@@ -810,6 +810,19 @@ def spmm(x, csr, y=None, alpha=1.0, z=None, beta=0.0):
     return set_rm(y, rm)
 
 
+def _fill_term(t, x, csr, vec_ok, scale=1.0):
+    """One CapeSpmmTerm: the view ``x`` and its operator (None or an identity DeviceCSR = identity term).  Without ``vec_ok`` the
+    launch takes the scalar fallback, which reads CSR only."""
+    xp, t.x_sample_stride, t.ldx = _v(x)
+    t.x = xp.value
+    t.scale = scale
+    if csr is None or csr.identity:
+        t.rowptr = t.colidx = t.vals = None
+    else:
+        t.rowptr, t.colidx, t.vals, t.ell_width = csr.operands() if vec_ok else \
+            (csr.rowptr_t.data_ptr(), csr.colidx_t.data_ptr(), csr.vals_t.data_ptr(), 0)
+
+
 def spmm_multi(xs, csrs, sum=False, scales=None, act_x=None, act=None):
     """Several operator applications in one launch: ``sum=False`` -> [s_k S_k x_k for k]; ``sum=True`` -> sum_k s_k S_k x_k
     (``scales`` default 1).  ``csrs[k]`` None or an identity DeviceCSR = identity term.  All operators have the same
@@ -826,17 +839,10 @@ def spmm_multi(xs, csrs, sum=False, scales=None, act_x=None, act=None):
     vec_ok = _vec_ok(*xs)          # (fresh outputs are row-padded: only the inputs decide; the ELL form needs the vector kernels)
     for k in range(n):
         assert xs[k].shape[0] == N and xs[k].shape[2] == Cn and (not ident[k] or xs[k].shape[1] == Mo)
-        t = arr[k]
-        xp, t.x_sample_stride, t.ldx = _v(xs[k])
-        t.x = xp.value
-        t.scale = 1.0 if scales is None else float(scales[k])
-        if ident[k]:
-            t.rowptr = t.colidx = t.vals = None
-        else:
-            assert csrs[k].shape[0] == Mo and csrs[k].shape[1] == xs[k].shape[1]
-            t.rowptr, t.colidx, t.vals, t.ell_width = csrs[k].operands() if vec_ok else \
-                (csrs[k].rowptr_t.data_ptr(), csrs[k].colidx_t.data_ptr(), csrs[k].vals_t.data_ptr(), 0)
+        assert ident[k] or (csrs[k].shape[0] == Mo and csrs[k].shape[1] == xs[k].shape[1])
         assert xs[k].dtype == xs[0].dtype
+        t = arr[k]
+        _fill_term(t, xs[k], csrs[k], vec_ok, 1.0 if scales is None else float(scales[k]))
         if not sum:
             yk = alloc_act(N, Mo, Cn, xs[0].device, dtype=xs[0].dtype)
             yp, t.y_sample_stride, t.ldy = _v(yk)
@@ -895,17 +901,10 @@ def spmm_combine(xs, csrs, y, to_acc2=0, rank=None, bias=None, bias_mode=_lib.BI
     arr = (_lib.CapeSpmmTerm * n)()
     vec_ok = _vec_ok(y, *xs)
     for k in range(n):
-        t = arr[k]
-        xp, t.x_sample_stride, t.ldx = _v(xs[k])
-        t.x = xp.value
         assert xs[k].shape[2] == F and xs[k].dtype == y.dtype
-        t.scale = 1.0
-        if csrs[k] is None or csrs[k].identity:
-            t.rowptr = t.colidx = t.vals = None
-        else:
-            assert csrs[k].shape[0] == Mo and csrs[k].shape[1] == xs[k].shape[1]
-            t.rowptr, t.colidx, t.vals, t.ell_width = csrs[k].operands() if vec_ok else \
-                (csrs[k].rowptr_t.data_ptr(), csrs[k].colidx_t.data_ptr(), csrs[k].vals_t.data_ptr(), 0)
+        assert csrs[k] is None or csrs[k].identity or (csrs[k].shape[0] == Mo and csrs[k].shape[1] == xs[k].shape[1])
+        t = arr[k]
+        _fill_term(t, xs[k], csrs[k], vec_ok)
         t.y, t.y_sample_stride, t.ldy = None, 0, 0
     rk = None
     if rank is not None:
@@ -1082,6 +1081,26 @@ def _finalize_bwd_prep(items):
         check(lib.cape_bwd_prep_finalize(arr, len(chunk), _stream()), "cape_bwd_prep_finalize")
 
 
+def _alloc_dcoef(N, R, F, dev, want_g, joint):
+    """The rank-1 condition gradients of a backward-prep: (dcoef [N, R, F] or None, dcoef_g [N, F] or None, their sample stride
+    for the C side).  ``joint``: both are slices of ONE [N, R+1, F] buffer, returned as dcoef."""
+    if joint and R and want_g:
+        dcoef = torch.empty((N, R + 1, F), device=dev, dtype=torch.float32)
+        return dcoef, dcoef[:, R], (R + 1) * F
+    dcoef = torch.empty((N, R, F), device=dev, dtype=torch.float32) if R else None
+    dcoef_g = torch.empty((N, F), device=dev, dtype=torch.float32) if want_g else None
+    return dcoef, dcoef_g, 0
+
+
+def _finish_bwd_prep(defer, done=False, **item):
+    """The final stage of one backward-prep's partials (``item``: see _finalize_bwd_prep): queued on DEFERRED, or run at once
+    unless the producing launch has ``done`` it already."""
+    if defer and DEFERRED is not None:
+        DEFERRED.append(item)
+    elif not done:
+        _finalize_bwd_prep([item])
+
+
 def bwd_prep(g, y=None, act="none", mask=None, want_bias=False, rowscale=None, R=0, rg=None, dbias_out=None, joint=False,
              defer=False):
     """One pass over g: returns (dz, dbias [F] or None, dcoef [N,R,F] or None, dcoef_g [N,F] or None).
@@ -1103,14 +1122,7 @@ def bwd_prep(g, y=None, act="none", mask=None, want_bias=False, rowscale=None, R
             dbias = dbias_out.view(F)
         else:
             dbias = torch.empty(F, device=dev, dtype=torch.float32)
-    cstride = 0
-    if joint and R and rg is not None:
-        dcoef = torch.empty((N, R + 1, F), device=dev, dtype=torch.float32)
-        dcoef_g = dcoef[:, R]
-        cstride = (R + 1) * F
-    else:
-        dcoef = torch.empty((N, R, F), device=dev, dtype=torch.float32) if R else None
-        dcoef_g = torch.empty((N, F), device=dev, dtype=torch.float32) if rg is not None else None
+    dcoef, dcoef_g, cstride = _alloc_dcoef(N, R, F, dev, rg is not None, joint)
     need = lib.cape_bwd_prep_workspace_bytes(N, Mo, F, R)
     ws = torch.empty((need + 3) // 4, device=dev, dtype=torch.float32)
     gp, gs, gl = _v(g)
@@ -1138,8 +1150,8 @@ def bwd_prep(g, y=None, act="none", mask=None, want_bias=False, rowscale=None, R
     # one pass: read g (+ y or the 1-bit mask), write dz
     _log_launch("bwd_prep", 0, g.element_size() * N * Mo * F * (1 if alias else 3 if yp is not None else 2) + (N * Mo * ((F + 31) // 32) * 4 if mask is not None else 0),
                 launch)
-    if defer and DEFERRED is not None and (dbias is not None or R or rg is not None):
-        DEFERRED.append(dict(ws=ws, N=N, Mo=Mo, F=F, R=R, dbias=dbias, dcoef=dcoef, dcoef_g=dcoef_g, cstride=cstride))
+    if dbias is not None or R or rg is not None:        # (undeferred, the launch ran its own final stage)
+        _finish_bwd_prep(defer, done=True, ws=ws, N=N, Mo=Mo, F=F, R=R, dbias=dbias, dcoef=dcoef, dcoef_g=dcoef_g, cstride=cstride)
     return dz, dbias, dcoef, dcoef_g
 
 
@@ -1160,14 +1172,7 @@ def bwd_prep_spmm(g, mask, csr, rowscale=None, R=0, rg=None, joint=False, defer=
     chunks = int(_fn("cape_bwd_prep_spmm_chunks", g)(gp, gs, gl, zp, zs, zl, tp, ts, tl, N, Mo, F))
     if chunks <= 0:
         return None
-    cstride = 0
-    if joint and R and rg is not None:
-        dcoef = torch.empty((N, R + 1, F), device=dev, dtype=torch.float32)
-        dcoef_g = dcoef[:, R]
-        cstride = (R + 1) * F
-    else:
-        dcoef = torch.empty((N, R, F), device=dev, dtype=torch.float32) if R else None
-        dcoef_g = torch.empty((N, F), device=dev, dtype=torch.float32) if rg is not None else None
+    dcoef, dcoef_g, cstride = _alloc_dcoef(N, R, F, dev, rg is not None, joint)
     need_part = bool(R) or rg is not None
     part = torch.empty((N, chunks, R + 2, F), device=dev, dtype=torch.float32) if need_part else None
     rp_, ci_, va_, ew_ = csr.operands()
@@ -1191,11 +1196,7 @@ def bwd_prep_spmm(g, mask, csr, rowscale=None, R=0, rg=None, joint=False, defer=
     _log_launch("bwd_prep_spmm", 2 * N * csr.nnz * F, g.element_size() * N * Mo * F * 3 + N * Mo * (F // 32) * 4 + 8 * csr.nnz, launch)
     set_rm(t1, rm_t1)
     if need_part:
-        item = dict(ws=part, N=N, Mo=Mo, F=F, R=R, dbias=None, dcoef=dcoef, dcoef_g=dcoef_g, cstride=cstride, chunks=chunks)
-        if defer and DEFERRED is not None:
-            DEFERRED.append(item)
-        else:
-            _finalize_bwd_prep([item])
+        _finish_bwd_prep(defer, ws=part, N=N, Mo=Mo, F=F, R=R, dbias=None, dcoef=dcoef, dcoef_g=dcoef_g, cstride=cstride, chunks=chunks)
     return dz, t1, dcoef, dcoef_g
 
 
@@ -1215,14 +1216,11 @@ def spmm_multi_prep(g, mask, csrs, masked, want_sums=True, joint=False, defer=Fa
     dev = g.device
     arr = (_lib.CapeSpmmTerm * n)()
     outs = []
-    gp, gs, gl = _v(g)
     bits = 0
     for k in range(n):
         assert csrs[k].shape[0] == Mo
         t = arr[k]
-        t.x, t.x_sample_stride, t.ldx = gp.value, gs, gl
-        t.scale = 1.0
-        t.rowptr, t.colidx, t.vals, t.ell_width = csrs[k].operands()
+        _fill_term(t, g, csrs[k], True)
         yk = alloc_act(N, Mo, F, dev, dtype=g.dtype)
         yp, t.y_sample_stride, t.ldy = _v(yk)
         t.y = yp.value
@@ -1237,15 +1235,8 @@ def spmm_multi_prep(g, mask, csrs, masked, want_sums=True, joint=False, defer=Fa
         return None
     R = n - 1
     dcoef = dcoef_g = part = None
-    cstride = 0
     if want_sums:
-        if joint:
-            dcoef = torch.empty((N, R + 1, F), device=dev, dtype=torch.float32)
-            dcoef_g = dcoef[:, R]
-            cstride = (R + 1) * F
-        else:
-            dcoef = torch.empty((N, R, F), device=dev, dtype=torch.float32)
-            dcoef_g = torch.empty((N, F), device=dev, dtype=torch.float32)
+        dcoef, dcoef_g, cstride = _alloc_dcoef(N, R, F, dev, True, joint)
         part = torch.empty((N, chunks, n + 1, F), device=dev, dtype=torch.float32)
     flops = sum(2 * N * c.nnz * F for c in csrs)
     byts = g.element_size() * N * F * (Mf + n * Mo) + N * Mf * (F // 32) * 4 + sum(_csr_bytes(c) for c in csrs)
@@ -1253,11 +1244,7 @@ def spmm_multi_prep(g, mask, csrs, masked, want_sums=True, joint=False, defer=Fa
                 lambda: check(_fn("cape_spmm_multi_prep", g)(arr, n, bits, _ptr(mask), Mf, N, Mo, F, _ptr(part),
                                                        0 if part is None else part.numel() * 4, _stream()), "cape_spmm_multi_prep"))
     if want_sums:
-        item = dict(ws=part, N=N, Mo=Mo, F=F, R=R, dbias=None, dcoef=dcoef, dcoef_g=dcoef_g, cstride=cstride, chunks=chunks)
-        if defer and DEFERRED is not None:
-            DEFERRED.append(item)
-        else:
-            _finalize_bwd_prep([item])
+        _finish_bwd_prep(defer, ws=part, N=N, Mo=Mo, F=F, R=R, dbias=None, dcoef=dcoef, dcoef_g=dcoef_g, cstride=cstride, chunks=chunks)
     return outs, dcoef, dcoef_g
 
 

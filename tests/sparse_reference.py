@@ -1,4 +1,4 @@
-"""Synthetic sparse operators and restatements of the streaming sparse-operator entry points (csrc/elementwise.hip: cape_spmm,
+"""Synthetic sparse operators and restatements of the streaming sparse-operator entry points (csrc/sparse.hip: cape_spmm,
 cape_spmm_multi[_actgrad], cape_bwd_prep_spmm, cape_spmm_multi_prep, cape_spmm_combine) for tests/test_gpu_sparse.py and
 tests/test_sparse_reference_host.py.  TEST INFRASTRUCTURE ONLY, no GPU.
 

@@ -1,4 +1,4 @@
-"""The streaming sparse-operator kernels (csrc/elementwise.hip: spmm_kernel, spmm_multi_kernel with its fused activation-gradient
+"""The streaming sparse-operator kernels (csrc/sparse.hip: spmm_kernel, spmm_multi_kernel with its fused activation-gradient
 epilogue, spmm_combine_kernel, bwd_prep_spmm_kernel, spmm_multi_prep_kernel and the gather helpers below them) on small synthetic
 operators (tests/sparse_reference.py): every ELL width with empty rows and rows of exactly 4, 5, 8, 9 and 12 entries, operators
 that must stay CSR, stored zeros, tail blocks, one and several blocks, both branches of the block mapping (N % 8), the chunked
@@ -25,7 +25,7 @@ from kernel_bars import element_bar, sum_bar, same_bits
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-WIDE = os.environ.get("CAPE_SPMM_WIDE") is None or int(os.environ["CAPE_SPMM_WIDE"]) != 0      # csrc/elementwise.hip spmm_wide()
+WIDE = os.environ.get("CAPE_SPMM_WIDE") is None or int(os.environ["CAPE_SPMM_WIDE"]) != 0      # csrc/views.h spmm_wide()
 SHAPES = [(37, 190), (300, 53), (37, 53), (300, 190)]            # (Mo, Mi): below one block of 256 work items / not a multiple
 NS = [1, 3, 8, 16]                                               # 8, 16: the N % 8 == 0 branch of cape_map_block
 F32, BF16 = torch.float32, torch.bfloat16

@@ -22,7 +22,6 @@ BIAS_NONE, BIAS_CHANNEL, BIAS_VERTEX = 0, 1, 2
 class CapeSrc(C.Structure):
     _fields_ = [
         ("x", C.c_void_p), ("x_sample_stride", C.c_int64), ("ldx", C.c_int32), ("C", C.c_int32),
-        ("rowptr", C.c_void_p), ("colidx", C.c_void_p), ("vals", C.c_void_p),
         ("w", C.c_void_p), ("w_rs", C.c_int64), ("w_cs", C.c_int64),
         ("w2", C.c_void_p), ("w2_rs", C.c_int64), ("w2_cs", C.c_int64),
     ]

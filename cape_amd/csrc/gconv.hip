@@ -1,15 +1,16 @@
-// Fused gather-GEMM for the Chebyshev mesh convolution (gfx950 / CDNA4, fp32 MFMA).
+// The trailing contraction of the Chebyshev mesh convolution (gfx950 / CDNA4, fp32 MFMA).
 //
-//   y[n, r, :] = epilogue( sum_s  (S_s x_s[n])[r, :] @ B_s )
+//   y[n, r, :] = epilogue( sum_s  x_s[n][r, :] @ B_s )
 //
-// S_s is a small CSR operator (a precomposed T_k(L~), T_k(L~)*U, D*T_k(L~) or a transpose of
-// one of those); the gathered A-tile [BM x 32] is built in LDS from coalesced float4 reads
-// of the [N, M, C] activations (neighbour rows come from L2: one mesh level of one sample is
-// <= 2.6 MB), the trailing dense contraction runs on v_mfma_f32_32x32x2_f32 (exact fp32).
-// This one kernel covers chebyshev5 (reference lib/models.py:69-103), the bias/activation
-// epilogues (:105-127), poolwT folded in as an operator (:129-152), res_block_affine in DUAL
-// mode (:776-793) and -- with transposed operators and weights -- their data gradients.
-// The weight-gradient kernel (contraction over vertices) lives below.
+// Every source x_s is a plain [N, Mo, C] view: the operators S_k (a precomposed T_k(L~), T_k(L~)*U,
+// D*T_k(L~) or a transpose of one of those) are applied beforehand by the streaming kernels of
+// sparse.hip.  The kernels of this file are the GENERIC form of that contraction: they stage the
+// A-tile [BM x 32] in LDS from rows of any alignment (channel-offset views, odd channel counts
+// without row padding) and multiply on v_mfma_f32_32x32x2_f32 (exact fp32); sources that allow it
+// take the pipelined kernels of gemm_plain.h / gemm_split.h / gemm_h2.h instead.
+// Together they cover chebyshev5 (reference lib/models.py:69-103), the bias/activation
+// epilogues (:105-127), res_block_affine in DUAL mode (:776-793) and -- with transposed weights --
+// their data gradients.  The weight-gradient kernel (contraction over vertices) lives below.
 #include "common.h"
 #include "gconv_shared.h"
 #include "gemm_plain.h"
@@ -24,10 +25,10 @@ namespace {
 
 constexpr int KC_DEFAULT = 32;   // contraction chunk staged per iteration
 
-// ---- A-tile staging: gathered rows -> LDS [ROWS][KC+4] -----------------------------------
+// ---- A-tile staging: source rows -> LDS [ROWS][KC+4] -------------------------------------
 template <int ROWS, int LDA, int KC, typename AT = float>
-__device__ __forceinline__ void stage_gather(float *sA, const SrcDev &S, int n, int r0, int Mo,
-                                              int c0, int tid) {
+__device__ __forceinline__ void stage_rows(float *sA, const SrcDev &S, int n, int r0, int Mo,
+                                            int c0, int tid) {
     constexpr int QPR = KC / 4;            // float4 columns per row of the chunk
     constexpr int RP = 256 / QPR;          // rows staged per pass
     const int q = tid % QPR;
@@ -37,8 +38,8 @@ __device__ __forceinline__ void stage_gather(float *sA, const SrcDev &S, int n, 
     const AT *xb = x0 + c;
     const int nvalid = S.C - c;   // channels available from c
     constexpr int P = ROWS / RP;
-    if (!S.rp && S.vec && (nvalid >= 4 || (nvalid > 0 && c + 4 <= S.ldx) || nvalid <= 0)) {
-        // plain source, aligned: issue every load of the chunk before the first LDS store.  A row
+    if (S.vec && (nvalid >= 4 || (nvalid > 0 && c + 4 <= S.ldx) || nvalid <= 0)) {
+        // aligned source: issue every load of the chunk before the first LDS store.  A row
         // padded to a multiple of 4 floats lets the last (partial) float4 be loaded whole; the lanes
         // beyond C are zeroed below (e.g. the 3-channel network input in a 4-float row).
         float4 v[P];
@@ -62,50 +63,17 @@ __device__ __forceinline__ void stage_gather(float *sA, const SrcDev &S, int n, 
     }
 #pragma unroll
     for (int pass = 0; pass < P; ++pass) {
+        // unaligned rows, or the last (partial) float4 of an unpadded row: element by element
         const int rl = rl0 + RP * pass;
         const int r = r0 + rl;
-        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        float a[4] = {0.f, 0.f, 0.f, 0.f};
         if (r < Mo && nvalid > 0) {
-            if (S.vec && nvalid >= 4) {
-                // gathered source: two row entries in flight per step
-                const int e1 = S.rp[r + 1];
-                int e = S.rp[r];
-                for (; e + 1 < e1; e += 2) {
-                    const float v0 = S.va[e], v1 = S.va[e + 1];
-                    const float4 xa = cape_ld4(xb + (long long)S.ci[e] * S.ldx);
-                    const float4 xc = cape_ld4(xb + (long long)S.ci[e + 1] * S.ldx);
-                    acc.x = fmaf(v0, xa.x, acc.x); acc.y = fmaf(v0, xa.y, acc.y);
-                    acc.z = fmaf(v0, xa.z, acc.z); acc.w = fmaf(v0, xa.w, acc.w);
-                    acc.x = fmaf(v1, xc.x, acc.x); acc.y = fmaf(v1, xc.y, acc.y);
-                    acc.z = fmaf(v1, xc.z, acc.z); acc.w = fmaf(v1, xc.w, acc.w);
-                }
-                if (e < e1) {
-                    const float v0 = S.va[e];
-                    const float4 xa = cape_ld4(xb + (long long)S.ci[e] * S.ldx);
-                    acc.x = fmaf(v0, xa.x, acc.x); acc.y = fmaf(v0, xa.y, acc.y);
-                    acc.z = fmaf(v0, xa.z, acc.z); acc.w = fmaf(v0, xa.w, acc.w);
-                }
-            } else {
-                float a[4] = {0.f, 0.f, 0.f, 0.f};
-                if (S.rp) {
-                    const int e1 = S.rp[r + 1];
-                    for (int e = S.rp[r]; e < e1; ++e) {
-                        const float v = S.va[e];
-                        const AT *xr = xb + (long long)S.ci[e] * S.ldx;
+            const AT *xr = xb + (long long)r * S.ldx;
 #pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (u < nvalid) a[u] = fmaf(v, cape_ld(xr + u), a[u]);
-                    }
-                } else {
-                    const AT *xr = xb + (long long)r * S.ldx;
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-                        if (u < nvalid) a[u] = cape_ld(xr + u);
-                }
-                acc = make_float4(a[0], a[1], a[2], a[3]);
-            }
+            for (int u = 0; u < 4; ++u)
+                if (u < nvalid) a[u] = cape_ld(xr + u);
         }
-        *reinterpret_cast<float4 *>(&sA[rl * LDA + 4 * q]) = acc;
+        *reinterpret_cast<float4 *>(&sA[rl * LDA + 4 * q]) = make_float4(a[0], a[1], a[2], a[3]);
     }
 }
 
@@ -179,10 +147,10 @@ __device__ __forceinline__ void stage_weights(float *sB, const float *w, long lo
     }
 }
 
-// Workgroup = 4 waves; every wave stages its share of the [BM x KC] gathered A chunk and the [KC x BN]
+// Workgroup = 4 waves; every wave stages its share of the [BM x KC] A chunk and the [KC x BN]
 // weight chunk, then multiplies.  3-4 resident workgroups per CU overlap each other's staging and MFMA
 // phases (measured faster here than a loader/MFMA wave split and than a register-prefetch pipeline, which
-// cost occupancy on the gather path; plain sources take the pipelined kernel of gemm_plain.h instead).
+// cost occupancy here; aligned sources take the pipelined kernel of gemm_plain.h instead).
 template <int BM, int BN, int WAVES_M, int WAVES_N, bool DUAL, int KC = KC_DEFAULT, typename AT = float>
 __global__ __launch_bounds__(256, 4) void gconv_fwd_kernel(GconvParams p) {
     constexpr int LDA = KC + 4;
@@ -231,7 +199,7 @@ __global__ __launch_bounds__(256, 4) void gconv_fwd_kernel(GconvParams p) {
         const SrcDev &S = p.s[l_si];
         float *sA = smem + buf * BUF_SZ;
         float *sB = sA + A_SZ;
-        stage_gather<BM, LDA, KC, AT>(sA, S, n, r0, p.Mo, l_c0, ltid);
+        stage_rows<BM, LDA, KC, AT>(sA, S, n, r0, p.Mo, l_c0, ltid);
         stage_weights<BN, LDB, 256, KC>(sB, S.w, S.wrs, S.wcs, S.C, p.F, l_c0, f0, ltid);
         if (DUAL && S.w2) stage_weights<BN, LDB, 256, KC>(sB + B_SZ, S.w2, S.w2rs, S.w2cs, S.C, p.F, l_c0, f0, ltid);
         l_c0 += KC;
@@ -352,9 +320,9 @@ __global__ __launch_bounds__(256, 4) void gconv_dw_kernel(DwParams p) {
 
     for (int rbase = ra; rbase < rb; rbase += RK) {
         __syncthreads();
-        // A chunk: RK (gathered) rows x CT channels
-        if (!S.rp && S.vec && (((S.C & 3) == 0) || (((S.C + 3) & ~3) <= S.ldx))) {
-            // plain aligned source: all loads first, clamped rows/columns + select (partial channel tiles
+        // A chunk: RK rows x CT channels
+        if (S.vec && (((S.C & 3) == 0) || (((S.C + 3) & ~3) <= S.ldx))) {
+            // aligned source: all loads first, clamped rows/columns + select (partial channel tiles
             // included: a float4 column is either entirely inside [0, C) or entirely outside)
             constexpr int NA = RK * (CT / 4) / 256;
             float4 va4[NA];
@@ -387,36 +355,13 @@ __global__ __launch_bounds__(256, 4) void gconv_dw_kernel(DwParams p) {
             float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
             if (r < rb && nvalid > 0) {
                 if (S.vec && nvalid >= 4) {
-                    if (S.rp) {
-                        const int e1 = S.rp[r + 1];
-                        for (int e = S.rp[r]; e < e1; ++e) {
-                            const float v = S.va[e];
-                            const float4 xv = cape_ld4(xb + (long long)S.ci[e] * S.ldx + c);
-                            v4.x = fmaf(v, xv.x, v4.x);
-                            v4.y = fmaf(v, xv.y, v4.y);
-                            v4.z = fmaf(v, xv.z, v4.z);
-                            v4.w = fmaf(v, xv.w, v4.w);
-                        }
-                    } else {
-                        v4 = cape_ld4(xb + (long long)r * S.ldx + c);
-                    }
+                    v4 = cape_ld4(xb + (long long)r * S.ldx + c);
                 } else {
                     float a[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (S.rp) {
-                        const int e1 = S.rp[r + 1];
-                        for (int e = S.rp[r]; e < e1; ++e) {
-                            const float v = S.va[e];
-                            const AT *xr = xb + (long long)S.ci[e] * S.ldx + c;
+                    const AT *xr = xb + (long long)r * S.ldx + c;
 #pragma unroll
-                            for (int u = 0; u < 4; ++u)
-                                if (u < nvalid) a[u] = fmaf(v, cape_ld(xr + u), a[u]);
-                        }
-                    } else {
-                        const AT *xr = xb + (long long)r * S.ldx + c;
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (u < nvalid) a[u] = cape_ld(xr + u);
-                    }
+                    for (int u = 0; u < 4; ++u)
+                        if (u < nvalid) a[u] = cape_ld(xr + u);
                     v4 = make_float4(a[0], a[1], a[2], a[3]);
                 }
             }
@@ -609,9 +554,7 @@ __global__ __launch_bounds__(256) void dw_reduce_batch_kernel(DwReduceBatch B) {
 // es = bytes per activation element (4: fp32, 2: bf16 storage)
 inline int fill_src(SrcDev &d, const cape_src_t &s, int es = 4) {
     if (!s.x || s.C <= 0 || s.ldx < s.C) return CAPE_EINVAL;
-    if (s.rowptr && (!s.colidx || !s.vals)) return CAPE_EINVAL;
     d.x = s.x; d.xs = s.x_sample_stride; d.ldx = s.ldx; d.C = s.C;
-    d.rp = s.rowptr; d.ci = s.colidx; d.va = s.vals;
     d.w = s.w; d.wrs = s.w_rs; d.wcs = s.w_cs;
     d.w2 = s.w2; d.w2rs = s.w2_rs; d.w2cs = s.w2_cs;
     d.vec = ((s.ldx & 3) == 0) && ((s.x_sample_stride & 3) == 0) && ((reinterpret_cast<uintptr_t>(s.x) & (4 * es - 1)) == 0);
@@ -653,7 +596,7 @@ struct DwPlan {
     long long slab;
 };
 
-// slots: workgroups the launch aims at.  512 = two per CU for the serial kernels (dw_split / dw_plain / dw_packed / gather: a
+// slots: workgroups the launch aims at.  512 = two per CU for the serial kernels (dw_split / dw_plain / dw_packed / generic: a
 // second workgroup hides their staging phase); 256 = one per CU for the pipelined dw_h2_kernel, which overlaps its phases
 // inside each wave -- half the partial slabs to write and to reduce: step 2.697 -> 2.670 ms in three alternating A/B pairs on one
 // box, the kernel itself 33 -> 37 us (profiles/r05_exp_dw_slots.txt); the same setting costs the serial bf16 kernels 5 %.
@@ -680,7 +623,7 @@ inline void plan_dw_splits(int N, int Mo, DwPlan &pl, int slots = DW_SLOTS_SERIA
     pl.ngroups = ngroups;
 }
 
-// gather kernel: one [ct x ft] tile grid per source
+// generic kernel: one [ct x ft] tile grid per source
 inline void plan_dw(const cape_src_t *srcs, int nsrc, int N, int Mo, int F, DwPlan &pl) {
     int maxC = 0;
     for (int i = 0; i < nsrc; ++i) maxC = srcs[i].C > maxC ? srcs[i].C : maxC;
@@ -724,12 +667,12 @@ inline void plan_dw_plain(const cape_src_t *srcs, int nsrc, int N, int Mo, int F
     plan_dw_splits(N, Mo, pl);
 }
 
-// Plain = no gather and float4-addressable rows.  A channel count that is not a multiple of 4 qualifies when the
+// Plain = float4-addressable rows.  A channel count that is not a multiple of 4 qualifies when the
 // row is padded to one (ld >= round_up(C, 4)): the pad lane only feeds an output row that is never stored
 // (the 3-channel network input / output layers).
 inline bool dw_srcs_plain(const cape_src_t *srcs, int nsrc, int es = 4) {
     for (int i = 0; i < nsrc; ++i)
-        if (srcs[i].rowptr || (((srcs[i].C + 3) & ~3) > srcs[i].ldx) || (srcs[i].ldx & 3) || (srcs[i].x_sample_stride & 3) ||
+        if ((((srcs[i].C + 3) & ~3) > srcs[i].ldx) || (srcs[i].ldx & 3) || (srcs[i].x_sample_stride & 3) ||
             (reinterpret_cast<uintptr_t>(srcs[i].x) & (4 * es - 1)))
             return false;
     return true;
@@ -751,19 +694,19 @@ inline void fill_h2_dw(DwParams &p, const cape_h2_dw_t *h2) {
     p.dz2rm = h2->dz2_rowmax; p.dz2rmw = h2->dz2_rowmax_w;
 }
 
-// Kernel choice of one weight-gradient launch (pure function of the arguments): 0 = gather form (gconv_dw_kernel),
+// Kernel choice of one weight-gradient launch (pure function of the arguments): 0 = generic form (gconv_dw_kernel),
 // 1 = pipelined plain kernel on the exact-fp32 MFMA (dw_plain_kernel), 2 = packed narrow sources (dw_packed_kernel),
 // 3 = plain sources on the bf16 pipe with the exact three-way operand split (dw_split_kernel).  Fills the tile plan.
 inline int choose_dw(const cape_src_t *srcs, int nsrc, const float *dz, int64_t dz_sample_stride, int32_t lddz,
                      const float *dz2, uint32_t dz2_mask, int N, int Mo, int F, DwPlan &pl, bool bf16 = false) {
-    static const int dwp_on = getenv("CAPE_DW_PLAIN") ? atoi(getenv("CAPE_DW_PLAIN")) : 1;      // 0: A/B against the gather kernel
+    static const int dwp_on = getenv("CAPE_DW_PLAIN") ? atoi(getenv("CAPE_DW_PLAIN")) : 1;      // 0: A/B against the generic kernel
     const int es = bf16 ? 2 : 4;
     const bool dzvec = dw_dz_vec(dz, dz_sample_stride, lddz, dz2, es);
     const bool plain = dwp_on && dzvec && (((F + 3) & ~3) <= lddz) && dw_srcs_plain(srcs, nsrc, es);
     if (bf16) {
         // bf16 storage: the split-pipe kernel with one plane where it applies (plain sources, whole float4-equivalent
         // columns, even F); the 3-channel ends take the pipelined fp32-MFMA kernels like the fp32 path (packed when
-        // several narrow sources share a tile, plain otherwise); the generic gather kernel for everything else
+        // several narrow sources share a tile, plain otherwise); the generic kernel for everything else
         bool c4b = true;
         int sumCb = 0;
         for (int i = 0; i < nsrc; ++i) { c4b = c4b && (srcs[i].C & 3) == 0; sumCb += srcs[i].C; }
@@ -796,7 +739,7 @@ inline int choose_dw(const cape_src_t *srcs, int nsrc, const float *dz, int64_t 
 // Kernel choice of one forward launch (pure function of the arguments).
 struct FwdPlan {
     int family;   // 4: plain sources with <= 8 input channels in total (fwd_narrow_in_kernel; plain epilogue only, else family 1)
-                  // 0: gather-GEMM (gconv_fwd_kernel), 1: pipelined plain GEMM (gemm_plain_kernel),
+                  // 0: generic staging for unaligned / unpadded sources (gconv_fwd_kernel), 1: pipelined plain GEMM (gemm_plain_kernel),
                   // 2: plain GEMM on the bf16 matrix pipe with exact three-way operand split (gemm_split_kernel)
                   // 3: plain GEMM as three fp16 products on two-piece operands (gemm_h2_kernel; needs cape_h2_t operands)
     int BM, BN;
@@ -805,11 +748,11 @@ struct FwdPlan {
 
 inline FwdPlan plan_fwd(const GconvParams &p, const cape_src_t *srcs, bool dual, bool bf16 = false) {
     FwdPlan pl;
-    static const int gp_on = getenv("CAPE_GEMM_PLAIN") ? atoi(getenv("CAPE_GEMM_PLAIN")) : 1;   // 0: A/B against the gather kernel
+    static const int gp_on = getenv("CAPE_GEMM_PLAIN") ? atoi(getenv("CAPE_GEMM_PLAIN")) : 1;   // 0: A/B against the generic kernel
     pl.layout = gp_on ? gp_weight_layout(p, dual) : -1;
     if (bf16) {
         // bf16 storage: the split-pipe kernel with one plane where its staging applies (plain sources of whole 32-channel
-        // chunks whose rows can be read 8 elements = 16 bytes at a time, F >= 64), the generic gather kernel otherwise
+        // chunks whose rows can be read 8 elements = 16 bytes at a time, F >= 64), the generic kernel otherwise
         bool ok = pl.layout >= 0 && p.F >= 64;
         for (int i = 0; i < p.nsrc && ok; ++i) {
             const long long ws = srcs[i].w_cs > srcs[i].w_rs ? srcs[i].w_cs : srcs[i].w_rs;
@@ -900,7 +843,7 @@ int gconv_fwd_plan_impl(const cape_src_t *srcs, int32_t nsrc, int32_t N, int32_t
 }
 
 template <typename AT>
-void launch_gather_fwd(const GconvParams &p, const FwdPlan &pl, bool dual, dim3 grid, hipStream_t st) {
+void launch_generic_fwd(const GconvParams &p, const FwdPlan &pl, bool dual, dim3 grid, hipStream_t st) {
     const dim3 block(256);
     if (!dual) {
         if (pl.BN == 32) CAPE_LAUNCH((gconv_fwd_kernel<128, 32, 4, 1, false, KC_DEFAULT, AT>), grid, block, 0, st, p);
@@ -972,9 +915,9 @@ int gconv_fwd_impl(const cape_src_t *srcs, int32_t nsrc, float *y, int64_t y_sam
     } else if (pl.family == 1) {
         gp_launch(p, dual, pl.BM, pl.BN, pl.layout, grid, st);
     } else if (bf16) {
-        launch_gather_fwd<cape_bf16>(p, pl, dual, grid, st);
+        launch_generic_fwd<cape_bf16>(p, pl, dual, grid, st);
     } else {
-        launch_gather_fwd<float>(p, pl, dual, grid, st);
+        launch_generic_fwd<float>(p, pl, dual, grid, st);
     }
     CAPE_LAUNCH_CHECK();
     return CAPE_OK;

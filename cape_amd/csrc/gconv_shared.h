@@ -1,5 +1,5 @@
-// Types and the output epilogue shared by the gather-GEMM kernels (gconv.hip) and the pipelined
-// plain-source GEMM (gemm_plain.h).  gfx950 only.
+// Types and the output epilogue shared by the generic contraction kernels (gconv.hip) and the pipelined
+// GEMM for aligned sources (gemm_plain.h).  gfx950 only.
 #pragma once
 #include "common.h"
 
@@ -9,14 +9,11 @@ struct SrcDev {
     const float *x;   // activations; reinterpreted as cape_bf16 by the bf16-storage kernels (strides in elements)
     long long xs;
     int ldx, C;
-    const int *rp;
-    const int *ci;
-    const float *va;
     const float *w;
     long long wrs, wcs;
     const float *w2;
     long long w2rs, w2cs;
-    int vec;   // 1: float4 gathers legal (ldx % 4 == 0, base 16B aligned)
+    int vec;   // 1: float4 row loads legal (ldx % 4 == 0, base 16B aligned)
     // fp16 two-piece path (gemm_h2.h): piece planes of the weight blocks [f][c] (pitch in halfs), row-maximum bounds of x
     const unsigned short *wh, *wl;
     long long wp;

@@ -857,7 +857,7 @@ inline bool h2_eligible(const GconvParams &p, bool dual) {
     if (!(ktot >= 256 || (ktot >= 128 && p.F >= 128))) return false;
     for (int i = 0; i < p.nsrc; ++i) {
         const SrcDev &S = p.s[i];
-        if (S.rp || !S.wh || !S.wl || !S.rm || S.rmw < 4 || S.rmw > 16 || (S.rmw & 3)) return false;
+        if (!S.wh || !S.wl || !S.rm || S.rmw < 4 || S.rmw > 16 || (S.rmw & 3)) return false;
         if (S.C % H2_KC != 0 || S.C < H2_KC) return false;
         if ((S.ldx & 3) || (S.xs & 3) || (reinterpret_cast<uintptr_t>(S.x) & 15)) return false;
         if ((long long)p.Mo * S.ldx >= (1LL << 29) || (long long)p.F * S.wp >= (1LL << 30)) return false;

@@ -1,4 +1,4 @@
-// Software-pipelined GEMM for PLAIN sources (no CSR gather): the second pass of the two-pass
+// Software-pipelined GEMM for PLAIN sources (float4-addressable rows): the second pass of the two-pass
 // Chebyshev convolution  y[n] = epilogue( sum_s X_s[n] @ B_s )  and its data gradient, where every
 // X_s is a materialised [N, Mo, C_s] activation (reference lib/models.py:99-102 -- the trailing
 // [N*M, Fin*K] x [Fin*K, Fout] contraction of chebyshev5).
@@ -590,7 +590,7 @@ inline int gp_weight_layout(const GconvParams &p, bool dual) {
     auto al16 = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     for (int i = 0; i < p.nsrc; ++i) {
         const SrcDev &S = p.s[i];
-        if (S.rp || !S.vec || (((S.C + 3) & ~3) > S.ldx) || !al16(S.w)) return -1;
+        if (!S.vec || (((S.C + 3) & ~3) > S.ldx) || !al16(S.w)) return -1;
         // contraction-contiguous weight rows are read as float4 along the contraction: whole float4s only
         kc = kc && (S.C & 3) == 0 && S.wrs == 1 && (S.wcs & 3) == 0 && S.wcs < (1LL << 20);
         nc = nc && S.wcs == 1 && (S.wrs & 3) == 0 && (p.F & 3) == 0;

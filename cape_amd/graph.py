@@ -1,4 +1,4 @@
-"""Host-side operator algebra for the fused gather-GEMM kernels.
+"""Host-side operator algebra for the sparse-operator and contraction kernels.
 
 The reference applies, per layer, a chain of fixed sparse matrices around a dense weight
 contraction: unpool ``U`` (lib/models.py:782), the Chebyshev recurrence in the rescaled

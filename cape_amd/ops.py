@@ -19,8 +19,9 @@ from .graph import ConvOperators, HostCSR
 # One evaluation form per layer: sparse operators applied by the streaming spmm kernels, dense contraction as a plain GEMM
 # ("two-pass").  The single-launch form of rounds 1-5 (operators gathered inside the GEMM's A-tile staging for WHOLE layers,
 # CAPE_MODE=fused) was slower at every mesh level and reached only 8 x the fp32 restatement's error on one data gradient where
-# the contract is 4 x (one fp32 MFMA chain per output element); it is gone.  The gather-form kernels themselves remain what the
-# library launches for sources that cannot be staged plainly (the 3-channel output layer), through the same C entry point.
+# the contract is 4 x (one fp32 MFMA chain per output element); it is gone, and with it the operator arguments of the
+# contraction kernels: a source is a plain view.  The generic kernels (gconv_fwd_kernel / gconv_dw_kernel) remain what the library
+# launches for sources that cannot be staged aligned (the 3-channel output layer), through the same C entry point.
 import os as _os
 # polynomial orders above the precomposed-operator limit: 1 = recurrence on chip where the layer qualifies
 # (csrc/cheb_fused.hip), 0 = always the materialised K-stack (ChebConvRecurrenceFn; the A/B reference)
@@ -150,9 +151,7 @@ class DeviceCSR(object):
         self.identity = host.identity
         self.nnz = host.nnz
         self.max_row, self.min_row = host.max_row, host.min_row
-        if host.identity:
-            self.rowptr = self.colidx = self.vals = None
-        else:
+        if not host.identity:
             rc = lib.cape_csr_validate(host.shape[0], host.shape[1], host.nnz,
                                        host.rowptr.ctypes.data_as(C.c_void_p),
                                        host.colidx.ctypes.data_as(C.c_void_p))
@@ -161,8 +160,6 @@ class DeviceCSR(object):
         self.rowptr_t = torch.from_numpy(host.rowptr).to(device)
         self.colidx_t = torch.from_numpy(host.colidx).to(device)
         self.vals_t = torch.from_numpy(host.vals).to(device)
-        if not host.identity:
-            self.rowptr, self.colidx, self.vals = self.rowptr_t, self.colidx_t, self.vals_t
         # ELL form for the streaming sparse kernels (None when the operator does not qualify)
         self.ell_w, self.ell_col_t, self.ell_val_t = 0, None, None
         ell = ell_arrays(host)
@@ -231,17 +228,12 @@ class DevicePatchPlan(object):
 
 
 def _mk_srcs(entries):
-    """entries: list of dict(x=view, csr=DeviceCSR|None, C=int, w=(tensor, off, rs, cs), w2=... or None)."""
+    """entries: list of dict(x=view, C=int, w=(tensor, off, rs, cs), w2=... or None)."""
     arr = (CapeSrc * len(entries))()
     for s, e in zip(arr, entries):
         x = e["x"]
         p, ss, ld = _v(x)
         s.x, s.x_sample_stride, s.ldx, s.C = p, ss, ld, int(e.get("C", x.shape[2]))
-        csr = e.get("csr")
-        if csr is not None and not csr.identity:
-            s.rowptr, s.colidx, s.vals = csr.rowptr.data_ptr(), csr.colidx.data_ptr(), csr.vals.data_ptr()
-        else:
-            s.rowptr = s.colidx = s.vals = None
         wt, off, rs, cs = e["w"]
         s.w, s.w_rs, s.w_cs = wt.data_ptr() + 4 * int(off), int(rs), int(cs)
         if e.get("w2") is not None:
@@ -283,8 +275,7 @@ def _trace_mask_bits(mask, F):
 
 
 def _gconv_work(entries, N, Mo, F):
-    """Algorithmic work of one gather-GEMM launch: dense contraction 2*N*Mo*C*F per weight block plus
-    2*N*nnz*C for the sparse operator application; bytes = operands touched once (fp32)."""
+    """Algorithmic work of one contraction launch: 2*N*Mo*C*F per weight block; bytes = operands touched once."""
     es = entries[0]["x"].element_size()
     flops, byts = 0, es * N * Mo * F
     seen = set()
@@ -292,10 +283,6 @@ def _gconv_work(entries, N, Mo, F):
         Cs = int(e.get("C", e["x"].shape[2]))
         nblk = 2 if e.get("w2") is not None else 1
         flops += 2 * N * Mo * Cs * F * nblk
-        csr = e.get("csr")
-        if csr is not None and not csr.identity:
-            flops += 2 * N * csr.nnz * Cs
-            byts += 8 * csr.nnz + 4 * (csr.shape[0] + 1)
         byts += 4 * Cs * F * nblk
         key = e["x"].data_ptr()
         if key not in seen:
@@ -1284,11 +1271,11 @@ class ChebConvFn(torch.autograd.Function):
     contribution is the rank-1 update (S_k 1)(cond_in W_k[cond rows]) added in the GEMM epilogue.
     ``cond_out`` [N, Cc'] is appended to the OUTPUT as materialised channels (only where a consumer
     needs the concatenated tensor, e.g. group-norm blocks).
-    ``mode``: "twopass" (the only form: X_k = S_k x by the streaming spmm kernels, then a plain multi-source GEMM).
+    One evaluation form: X_k = S_k x by the streaming spmm kernels, then a plain multi-source GEMM.
     """
 
     @staticmethod
-    def forward(ctx, x, W, bias, W_aff, cond_in, cond_out, ops, act, bias_mode, mode, gW=None, gWa=None, gB=None,
+    def forward(ctx, x, W, bias, W_aff, cond_in, cond_out, ops, act, bias_mode, gW=None, gWa=None, gB=None,
                 coef=None):
         x = as_act(x)
         if (x.shape[2] & 3) and (x.stride(1) & 3):
@@ -1309,29 +1296,26 @@ class ChebConvFn(torch.autograd.Function):
         Co = 0 if cond_out is None else cond_out.shape[1]
         yfull = alloc_act(N, ops.Mo, Fout + Co, x.device, dtype=x.dtype)
         y = yfull[:, :, :Fout]
-        assert mode == "twopass"
-        twopass = True
-        # up-sampling layer in two-pass mode: contract on the coarse rows, apply the operators to the products
+        # up-sampling layer: contract on the coarse rows, apply the operators to the products
         # (only when backward will not ask for the fine-level X_k: inference, or the coarse weight-gradient form)
         any_grad = any(ctx.needs_input_grad[i] for i in (0, 1, 2, 3, 4))
-        coarse = bool(twopass and ops.Mo > Mi and not any(ops.fwd[k].identity for k in range(K))
+        coarse = bool(ops.Mo > Mi and not any(ops.fwd[k].identity for k in range(K))
                       and (W_aff is None or Fout % 32 == 0) and Fout % 4 == 0 and (ctx.needs_input_grad[0] or not any_grad))
         if coarse:
             return ChebConvFn._forward_coarse(ctx, x, W, bias, W_aff, cond_in, cond_out, ops, act, bias_mode, gW, gWa, gB, coef,
                                               banked, Cc, yfull, y)
         xs = [x] * K
-        if twopass:
-            ks = [k for k in range(K) if not ops.fwd[k].identity]
-            if len(ks) == 1:
-                xs[ks[0]] = spmm(x, ops.fwd[ks[0]])
-            elif ks:                                   # X_k = S_k x of all orders in one launch
-                for k, xk in zip(ks, spmm_multi([x] * len(ks), [ops.fwd[k] for k in ks])):
-                    xs[k] = xk
-        P, Pa = ChebConvFn._pieces(x, W, W_aff, Ch, K, Fout, twopass)
+        ks = [k for k in range(K) if not ops.fwd[k].identity]
+        if len(ks) == 1:
+            xs[ks[0]] = spmm(x, ops.fwd[ks[0]])
+        elif ks:                                   # X_k = S_k x of all orders in one launch
+            for k, xk in zip(ks, spmm_multi([x] * len(ks), [ops.fwd[k] for k in ks])):
+                xs[k] = xk
+        P, Pa = ChebConvFn._pieces(x, W, W_aff, Ch, K, Fout)
         fw_ok = P is not None and Ch % 32 == 0 and h2_shape_ok(Ch * K, Fout)      # (forward planes: whole 32-channel chunks)
         entries = []
         for k in range(K):
-            e = dict(x=xs[k], csr=None, w=(W, k * Fout, K * Fout, 1))
+            e = dict(x=xs[k], w=(W, k * Fout, K * Fout, 1))
             if W_aff is not None and k == 0:
                 e["w2"] = (W_aff, 0, Fout, 1)
             if fw_ok:
@@ -1374,12 +1358,12 @@ class ChebConvFn(torch.autograd.Function):
         elif rm_y is not None:
             set_rm(yfull, rm_y)
         ctx.ops, ctx.act, ctx.bias_mode, ctx.Fout, ctx.Co, ctx.Cc = ops, act, bias_mode, Fout, Co, Cc
-        ctx.has_bias, ctx.twopass, ctx.xshape = bias is not None, twopass, (N, Mi, Ch)
+        ctx.has_bias, ctx.xshape = bias is not None, (N, Mi, Ch)
         ctx.gW, ctx.gWa, ctx.gB, ctx.banked = gW, gWa, gB, banked
         ctx.pieces = (P, Pa)
         # sole-consumer chain (see sole_consumer_chain): x is the output of a layer whose bias + (leaky-)ReLU epilogue this
         # layer's backward may differentiate for it; our own output is tagged the same way for the layer above
-        ctx.prev_act = getattr(x, "_cape_act_out", None) if (_CHAIN[0] and FUSE_ACT_GRAD and twopass) else None
+        ctx.prev_act = getattr(x, "_cape_act_out", None) if (_CHAIN[0] and FUSE_ACT_GRAD) else None
         ctx.offers_dz = bool(W_aff is None and Co == 0 and Cc == 0 and bias is not None and bias_mode == _lib.BIAS_CHANNEL
                              and act in ("leaky", "relu") and y.dtype in ACT_DTYPES and gB is not None)
         ctx.offer = None
@@ -1388,16 +1372,16 @@ class ChebConvFn(torch.autograd.Function):
         # up-sampling layers (Mo > Mi): the data gradient needs T_k = S_k^T dz at the Mi input rows anyway, and
         # dW_k = X_k^T dz = x^T T_k -- the weight gradient contracts over the COARSE rows (half the flops) and the
         # fine-level X_k need not be kept for the backward pass at all
-        ctx.coarse_dw = bool(twopass and ops.Mo > Mi and ctx.needs_input_grad[0] and not any(ops.fwd[k].identity for k in range(K)))
+        ctx.coarse_dw = bool(ops.Mo > Mi and ctx.needs_input_grad[0] and not any(ops.fwd[k].identity for k in range(K)))
         ctx.save_for_backward(W, W_aff, mask, yfull if (act != "none" and W_aff is None) else None, cond_in,
                               *(([x] if ctx.coarse_dw else list(xs)) + ([x] if ctx.prev_act is not None else [])))
         return yfull
 
     @staticmethod
-    def _pieces(x, W, W_aff, Ch, K, Fout, twopass):
+    def _pieces(x, W, W_aff, Ch, K, Fout):
         """Piece planes of the layer's weights when its contractions may run on the fp16 two-piece kernel (fp32 storage,
-        two-pass mode, whole 32-channel chunks on one side at least), else (None, None)."""
-        if not (H2 and twopass and x.dtype == torch.float32 and Ch % 8 == 0 and Fout % 8 == 0 and
+        whole 32-channel chunks on one side at least), else (None, None)."""
+        if not (H2 and x.dtype == torch.float32 and Ch % 8 == 0 and Fout % 8 == 0 and
                 ((Ch % 32 == 0 and Fout >= 64) or (Fout % 32 == 0 and Ch >= 64))):
             return None, None
         P = pieces_for(W, Ch, K, pair=(W_aff.detach(), 1) if W_aff is not None else None)
@@ -1413,24 +1397,24 @@ class ChebConvFn(torch.autograd.Function):
         and the epilogue.  Backward is the ordinary one in its coarse weight-gradient form (needs only x)."""
         N, Mi, Ch = x.shape
         K, Fout = ops.K, W.shape[1]
-        P, Pa = ChebConvFn._pieces(x, W, W_aff, Ch, K, Fout, True)
+        P, Pa = ChebConvFn._pieces(x, W, W_aff, Ch, K, Fout)
         fwd_ok = P is not None and Ch % 32 == 0 and h2_shape_ok(Ch, Fout)          # (K * Fout and Fout output columns)
         rmx = rowmax(x) if fwd_ok else None
         Z = alloc_act(N, Mi, K * Fout, x.device, dtype=x.dtype)
         if fwd_ok:
-            gconv_fwd([dict(x=x, csr=None, w=(W, 0, K * Fout, 1), p=(P.f_hi.data_ptr(), P.f_lo.data_ptr(), Ch), rm=rmx)], Z,
+            gconv_fwd([dict(x=x, w=(W, 0, K * Fout, 1), p=(P.f_hi.data_ptr(), P.f_lo.data_ptr(), Ch), rm=rmx)], Z,
                       wsi=_ptr(P.fsi))
         else:
-            gconv_fwd([dict(x=x, csr=None, w=(W, 0, K * Fout, 1))], Z)
+            gconv_fwd([dict(x=x, w=(W, 0, K * Fout, 1))], Z)
         zs = [Z[:, :, k * Fout:(k + 1) * Fout] for k in range(K)]
         csrs = [ops.fwd[k] for k in range(K)]
         to2 = 0
         if W_aff is not None:
             Za = alloc_act(N, Mi, Fout, x.device, dtype=x.dtype)
             if fwd_ok:
-                gconv_fwd([dict(x=x, csr=None, w=(W_aff, 0, Fout, 1), p=Pa.fwd(0), rm=rmx)], Za, wsi=_ptr(Pa.fsi))
+                gconv_fwd([dict(x=x, w=(W_aff, 0, Fout, 1), p=Pa.fwd(0), rm=rmx)], Za, wsi=_ptr(Pa.fsi))
             else:
-                gconv_fwd([dict(x=x, csr=None, w=(W_aff, 0, Fout, 1))], Za)
+                gconv_fwd([dict(x=x, w=(W_aff, 0, Fout, 1))], Za)
             zs.append(Za)
             csrs.append(ops.fwd[0])
             to2 = 1 << K
@@ -1460,7 +1444,7 @@ class ChebConvFn(torch.autograd.Function):
         else:
             set_rm(yfull, rm_of(y))         # (y is a view of yfull: the bounds spmm_combine wrote belong to the returned object too)
         ctx.ops, ctx.act, ctx.bias_mode, ctx.Fout, ctx.Co, ctx.Cc = ops, act, bias_mode, Fout, Co, Cc
-        ctx.has_bias, ctx.twopass, ctx.xshape = bias is not None, True, (N, Mi, Ch)
+        ctx.has_bias, ctx.xshape = bias is not None, (N, Mi, Ch)
         ctx.gW, ctx.gWa, ctx.gB, ctx.banked = gW, gWa, gB, banked
         ctx.coarse_dw = True
         ctx.pieces = (P, Pa)
@@ -1475,7 +1459,7 @@ class ChebConvFn(torch.autograd.Function):
         if getattr(ctx, "prev_act", None) is not None:
             xs, act_x = xs[:-1], xs[-1]                 # (the layer input itself: the output of the layer below)
         ops, act, Fout, Co, Cc = ctx.ops, ctx.act, ctx.Fout, ctx.Co, ctx.Cc
-        K, twopass = ops.K, ctx.twopass
+        K = ops.K
         N, Mi, Ch = ctx.xshape
         Mo, dev = ops.Mo, W.device
         gfull = as_act(gfull)
@@ -1514,13 +1498,13 @@ class ChebConvFn(torch.autograd.Function):
                          # results read only at the end of the backward pass (bucket view / CondCoefFn)
                          defer=(not chan_bias or ctx.gB is not None) and (not Cc or ctx.banked))
             fused_t1 = None
-            if (W_aff is not None and mask is not None and not chan_bias and need_x and K == 2 and Mo == Mi and Ch >= Fout and twopass
+            if (W_aff is not None and mask is not None and not chan_bias and need_x and K == 2 and Mo == Mi and Ch >= Fout
                     and ops.bwd[0].identity and not ops.bwd[1].identity and not ctx.coarse_dw):
                 # affine block at one resolution: dz, T_1 = L~^T dz and the condition sums in one launch
                 fused_t1 = bwd_prep_spmm(g, mask, ops.bwd[1], **bp_kw)
             fused_ts = None
             if (fused_t1 is None and W_aff is not None and mask is not None and not ctx.has_bias and need_x and K == 2 and ctx.coarse_dw
-                    and twopass and not any(ops.bwd[k].identity for k in range(K))):
+                    and not any(ops.bwd[k].identity for k in range(K))):
                 # up-sampling affine block: T_0, T_1 (from dz = g * sign bits, formed while gathering) and T_aff (from g) in one
                 # launch, the condition sums as their column sums; dz itself is needed by nobody (the weight gradient contracts
                 # the T_k: coarse_dw)
@@ -1543,9 +1527,8 @@ class ChebConvFn(torch.autograd.Function):
                 colsum(dz, dB, per_vertex=True)
             else:
                 dB = dbv.view(1, 1, Fout)
-        if dz is not None and H2 and twopass and dz.dtype == torch.float32 and rm_of(dz) is None and Fout % 32 == 0 and Fout >= 64 and (need_w or need_x):
+        if dz is not None and H2 and dz.dtype == torch.float32 and rm_of(dz) is None and Fout % 32 == 0 and Fout >= 64 and (need_w or need_x):
             rowmax(dz)      # (a gradient without bounds, e.g. from a group norm: one pass now serves the weight AND the data gradient)
-        csr_of = lambda k: None
         if need_w:
             dW = _grad_buffer(W, ctx.gW)
         if W_aff is not None and need_wa:
@@ -1554,9 +1537,9 @@ class ChebConvFn(torch.autograd.Function):
         if ctx.coarse_dw:
             pass                                   # computed from the T_k below
         elif need_w:
-            ent += [dict(x=xs[k], csr=csr_of(k), w=(dW, k * Fout, K * Fout, 1)) for k in range(K)]
+            ent += [dict(x=xs[k], w=(dW, k * Fout, K * Fout, 1)) for k in range(K)]
         if W_aff is not None and need_wa and not ctx.coarse_dw:
-            ent.append(dict(x=xs[0], csr=csr_of(0), w=(dWa, 0, Fout, 1), use_dz2=True))
+            ent.append(dict(x=xs[0], w=(dWa, 0, Fout, 1), use_dz2=True))
         # the slab reductions may wait for the end of the backward pass when every gradient block is a bucket view
         in_bucket = lambda t, v: t is None or (v is not None and t.data_ptr() == v.data_ptr())
         dw_defer = in_bucket(dW, ctx.gW) and in_bucket(dWa, ctx.gWa)
@@ -1598,7 +1581,7 @@ class ChebConvFn(torch.autograd.Function):
             bw_ok = P is not None and Fout % 32 == 0 and Ch >= 64 and g.dtype == torch.float32 and h2_shape_ok(ktot_bw, Ch)
 
             def src(xk, k, aff=False):
-                e = dict(x=xk, csr=None, w=waT if aff else wT(k))
+                e = dict(x=xk, w=waT if aff else wT(k))
                 if bw_ok:
                     e["p"], e["rm"] = (Pa.bwd(0) if aff else P.bwd(k)), rowmax(xk)
                 return e
@@ -1609,10 +1592,10 @@ class ChebConvFn(torch.autograd.Function):
                 ChP = _pad4(Ch)
                 Gall = alloc_act(N, Mo, K * ChP, dev, dtype=gfull.dtype)
                 if bw_ok:
-                    gconv_fwd([dict(x=dz, csr=None, w=(W, 0, 1, Fout), p=(P.b_hi.data_ptr(), P.b_lo.data_ptr(), Fout), rm=rowmax(dz))],
+                    gconv_fwd([dict(x=dz, w=(W, 0, 1, Fout), p=(P.b_hi.data_ptr(), P.b_lo.data_ptr(), Fout), rm=rowmax(dz))],
                               Gall, deinterleave=K, F=K * Ch, wsi=_ptr(P.bsi))
                 else:
-                    gconv_fwd([dict(x=dz, csr=None, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Ch)
+                    gconv_fwd([dict(x=dz, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Ch)
                 Gs = [Gall[:, :, k * ChP:k * ChP + Ch] for k in range(K)]
                 fused = None
                 if act_x is not None and actgrad_fusable(Gs, act_x, Ch) and tuple(act_x.shape) == (N, Mi, Ch):
@@ -1684,14 +1667,14 @@ class ChebConvFn(torch.autograd.Function):
                     # dW_k^T[f, c] = sum_{n, r} T_k[n, r, f] x[n, r, c]: the T_k are the sources, x the gradient operand
                     wen = []
                     if need_w:
-                        wen += [dict(x=Ts[k], csr=None, w=(dW, k * Fout, 1, K * Fout)) for k in range(K)]
+                        wen += [dict(x=Ts[k], w=(dW, k * Fout, 1, K * Fout)) for k in range(K)]
                     if W_aff is not None and need_wa:
-                        wen.append(dict(x=Ts[K], csr=None, w=(dWa, 0, 1, Fout)))
+                        wen.append(dict(x=Ts[K], w=(dWa, 0, 1, Fout)))
                     if wen:
                         gconv_dw(wen, xs[0], defer=dw_defer)
         if Co and need_co:
             dco = reduce_cond(gfull[:, :, Fout:])
-        return dx, dW, dB, dWa, dci, dco, None, None, None, None, None, None, None, dcoef_out
+        return dx, dW, dB, dWa, dci, dco, None, None, None, None, None, None, dcoef_out
 
 
 class ChebConvRecurrenceFn(torch.autograd.Function):
@@ -1707,7 +1690,7 @@ class ChebConvRecurrenceFn(torch.autograd.Function):
         for k in range(2, K):
             xs.append(spmm(xs[-1], ops.Lt, alpha=2.0, z=xs[-2], beta=-1.0))
         y = alloc_act(N, M, Fout, x.device)
-        gconv_fwd([dict(x=xs[k], csr=None, w=(W, k * Fout, K * Fout, 1)) for k in range(K)], y,
+        gconv_fwd([dict(x=xs[k], w=(W, k * Fout, K * Fout, 1)) for k in range(K)], y,
                   bias=bias, bias_mode=bias_mode, act=act)
         _trace_sign(y, act)
         ctx.ops, ctx.act, ctx.bias_mode, ctx.has_bias = ops, act, bias_mode, bias is not None
@@ -1734,13 +1717,13 @@ class ChebConvRecurrenceFn(torch.autograd.Function):
                 colsum(dz, dB)
         if ctx.needs_input_grad[1] and not skip_w:
             dW = torch.empty_like(W)
-            gconv_dw([dict(x=xs[k], csr=None, w=(dW, k * Fout, K * Fout, 1)) for k in range(K)], dz)
+            gconv_dw([dict(x=xs[k], w=(dW, k * Fout, K * Fout, 1)) for k in range(K)], dz)
         if ctx.needs_input_grad[0]:
             # all G_k = dz W_k^T in ONE launch (de-interleaving epilogue), then Clenshaw for sum_k T_k(L~)^T G_k with
             # every step  b_k = 2 L~^T b_{k+1} + G_k - b_{k+2}  as one scaled multi-term launch
             CP = _pad4(Cin)
             Gall = alloc_act(N, M, K * CP, g.device)
-            gconv_fwd([dict(x=dz, csr=None, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Cin)
+            gconv_fwd([dict(x=dz, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Cin)
             G = [Gall[:, :, k * CP:k * CP + Cin] for k in range(K)]
             b1 = b2 = None   # b_{k+1}, b_{k+2}
             for k in range(K - 1, 0, -1):
@@ -1870,7 +1853,7 @@ class ResidualLinearFn(torch.autograd.Function):
         assert W.shape == (Cx, F) and Wr.shape == (Cr, F) and W.is_contiguous() and Wr.is_contiguous() and r.shape[:2] == (N, M)
         Cc = 0 if cond is None else cond.shape[1]
         yfull = alloc_act(N, M, F + Cc, x.device, dtype=x.dtype)
-        e = [dict(x=x, csr=None, w=(W, 0, F, 1)), dict(x=r, csr=None, w=(Wr, 0, F, 1))]
+        e = [dict(x=x, w=(W, 0, F, 1)), dict(x=r, w=(Wr, 0, F, 1))]
         # fp16 two-piece operands: the two products add into one accumulator, so the two weights share their column scales
         P = Pr = None
         if H2 and x.dtype == torch.float32 and Cx % 32 == 0 and Cr % 32 == 0 and F % 8 == 0 and h2_shape_ok(Cx + Cr, F):
@@ -1910,25 +1893,25 @@ class ResidualLinearFn(torch.autograd.Function):
         ent = []
         if need_w:
             dW = _grad_buffer(W, ctx.gW)
-            ent.append(dict(x=x, csr=None, w=(dW, 0, F, 1)))
+            ent.append(dict(x=x, w=(dW, 0, F, 1)))
         if need_wr:
             dWr = _grad_buffer(Wr, ctx.gWr)
-            ent.append(dict(x=r, csr=None, w=(dWr, 0, F, 1)))
+            ent.append(dict(x=r, w=(dWr, 0, F, 1)))
         if ent:
             in_bucket = lambda t, v: t is None or (v is not None and t.data_ptr() == v.data_ptr())
             gconv_dw(ent, g, defer=in_bucket(dW, ctx.gW) and in_bucket(dWr, ctx.gWr))
         if need_x:
             dx = alloc_act(N, M, Cx, x.device, dtype=g.dtype)
             if bw and Cx >= 64 and h2_shape_ok(F, Cx):
-                gconv_fwd([dict(x=g, csr=None, w=(W, 0, 1, F), p=P.bwd(0), rm=rowmax(g))], dx, wsi=_ptr(P.bsc))
+                gconv_fwd([dict(x=g, w=(W, 0, 1, F), p=P.bwd(0), rm=rowmax(g))], dx, wsi=_ptr(P.bsc))
             else:
-                gconv_fwd([dict(x=g, csr=None, w=(W, 0, 1, F))], dx)          # W^T read in place (contraction index contiguous)
+                gconv_fwd([dict(x=g, w=(W, 0, 1, F))], dx)          # W^T read in place (contraction index contiguous)
         if need_r:
             dr = alloc_act(N, M, Cr, x.device, dtype=g.dtype)
             if bw and Cr >= 64 and h2_shape_ok(F, Cr):
-                gconv_fwd([dict(x=g, csr=None, w=(Wr, 0, 1, F), p=Pr.bwd(0), rm=rowmax(g))], dr, wsi=_ptr(Pr.bsc))
+                gconv_fwd([dict(x=g, w=(Wr, 0, 1, F), p=Pr.bwd(0), rm=rowmax(g))], dr, wsi=_ptr(Pr.bsc))
             else:
-                gconv_fwd([dict(x=g, csr=None, w=(Wr, 0, 1, F))], dr)
+                gconv_fwd([dict(x=g, w=(Wr, 0, 1, F))], dr)
         if ctx.Cc and need_c:
             dc = reduce_cond(gfull[:, :, F:])
         return dx, dr, dW, dWr, dc, None, None
@@ -2264,7 +2247,7 @@ def chebyshev5(x, W, ops, bias=None, activation=None, cond=None, W_affine=None, 
     else:
         act, bmode = _ACT_OF[activation]
     if ops.fused:
-        return ChebConvFn.apply(x, W, bias, W_affine, cond_in, cond, ops, act, bmode, "twopass", grad_bufs[0], grad_bufs[1],
+        return ChebConvFn.apply(x, W, bias, W_affine, cond_in, cond, ops, act, bmode, grad_bufs[0], grad_bufs[1],
                                 bias_grad_buf, coef)
     assert W_affine is None and coef is None
     if cond_in is not None:

@@ -19,14 +19,12 @@
  * (lib/models.py:81-83, 97-99, 147-151).
  *
  * Reference interfaces replaced (paths relative to the reference checkout):
- *   cape_gconv_fwd      lib/models.py:69-103  chebyshev5   (tf.sparse_tensor_dense_matmul x(K-1)
- *                                                           + tf.matmul), fused with
+ *   cape_gconv_fwd      lib/models.py:69-103  chebyshev5   (the tf.matmul; its tf.sparse_tensor_dense_matmul x(K-1)
+ *                                                           and poolwT, :129-152, are cape_spmm*), fused with
  *                       lib/models.py:105-127 b1leakyrelu / b1relu / b1tanh / b2relu,
- *                       lib/models.py:129-152 poolwT       (pool folded in as output-row CSR,
- *                                                           unpool folded in as input CSR),
  *                       lib/models.py:776-793 res_block_affine (DUAL accumulator mode),
  *                       lib/models.py:611-616 per-vertex output bias;
- *                       and, with transposed operators/weights, the data gradient that
+ *                       and, with transposed weights, the data gradient that
  *                       tf.gradients (lib/models.py:460,465) derives for those ops.
  *   cape_gconv_dw       the weight gradient of the same ops (tf.gradients, :460).
  *   cape_cheb_fused_fwd / cape_cheb_fused_bwd
@@ -72,7 +70,7 @@
 extern "C" {
 #endif
 
-#define CAPE_ABI_VERSION 16
+#define CAPE_ABI_VERSION 17
 #define CAPE_MAX_SRC 8
 
 /* error codes (negative = argument error; positive values are hipError_t) */
@@ -94,24 +92,20 @@ extern "C" {
 #define CAPE_BIAS_VERTEX 2     /* [1,M,F]  (b2relu, :615 output) */
 
 /*
- * One operand ("source") of the fused gather-GEMM:
- *   A[n, r, c] = sum_e vals[e] * x[n, colidx[e], c]   e in [rowptr[r], rowptr[r+1])
- *              = x[n, r, c]                            when rowptr == NULL (identity)
- *   acc1[n, r, f] += sum_c A[n, r, c] * w [c*w_rs  + f*w_cs ]
- *   acc2[n, r, f] += sum_c A[n, r, c] * w2[c*w2_rs + f*w2_cs]   (only if w2 != NULL)
+ * One operand ("source") of the contraction: a plain [N, Mo, C] view x (any row stride, any channel offset)
+ *   acc1[n, r, f] += sum_c x[n, r, c] * w [c*w_rs  + f*w_cs ]
+ *   acc2[n, r, f] += sum_c x[n, r, c] * w2[c*w2_rs + f*w2_cs]   (only if w2 != NULL)
+ * Operators are applied beforehand: the source of Chebyshev term k is S_k x, written by cape_spmm* (or, in the
+ * backward pass, by cape_bwd_prep_spmm / cape_spmm_multi_prep).
  * For the forward Chebyshev term k of a layer with reference weight W[Fin*K, Fout]
  * (row index fin*K + k, lib/models.py:97-101):  w = W + k*Fout, w_rs = K*Fout, w_cs = 1.
- * For its data gradient: x = dZ, CSR = transposed operator, w = W + k*Fout, w_rs = 1,
- * w_cs = K*Fout.
+ * For its data gradient: x = dZ, w = W + k*Fout, w_rs = 1, w_cs = K*Fout, and S_k^T is applied to the result.
  */
 typedef struct cape_src {
     const float *x;          /* device [N, Mi, ldx] (pointer may include a channel offset) */
     int64_t x_sample_stride; /* elements between consecutive samples                       */
     int32_t ldx;             /* row stride in elements                                     */
     int32_t C;               /* channels contracted from this source                       */
-    const int32_t *rowptr;   /* device, Mo+1 entries, or NULL for identity                 */
-    const int32_t *colidx;   /* device, nnz                                                */
-    const float *vals;       /* device, nnz                                                */
     const float *w;          /* device weight block 1                                      */
     int64_t w_rs, w_cs;
     const float *w2;         /* device weight block 2 (DUAL mode) or NULL                  */
@@ -119,7 +113,7 @@ typedef struct cape_src {
 } cape_src_t;
 
 /*
- * Rank-1 epilogue terms of the fused gather-GEMM: vertex-constant input channels (the tiled
+ * Rank-1 epilogue terms of the contraction: vertex-constant input channels (the tiled
  * condition vector, lib/models.py:813-832 fit_cond_dim + tf.concat at :593,608,665) need no
  * per-vertex contraction because S_k (1 c^T) = (S_k 1) c^T.  Their contribution to the
  * pre-activation is   sum_j rowscale[j, r] * coef[n, j, f]   with rowscale_j = S_k 1 (row sums of the
@@ -164,7 +158,7 @@ int cape_csr_validate(int32_t rows, int32_t cols, int64_t nnz, const int32_t *ro
                       const int32_t *colidx);
 
 /*
- * Fused gather-GEMM forward.
+ * The contraction, forward.
  *   single mode (mask_out == NULL, no source has w2):
  *        y[n,r,f] = act(acc1 + bias)
  *   DUAL mode (at least one source has w2)  -- res_block_affine, lib/models.py:776-793:
@@ -176,7 +170,7 @@ int cape_csr_validate(int32_t rows, int32_t cols, int64_t nnz, const int32_t *ro
  *   k * round_up(F/K, 4) + c, i.e. the reference's fin*K + k weight-row order (lib/models.py:97-101) comes out as
  *   K contiguous channel blocks -- ONE launch  G = dz W^T  for all K orders of a data gradient, each block then
  *   being the operand of its S_k^T (ldy >= K * round_up(F/K, 4)).  0 / 1 = off.
- * Arithmetic: fp32 in, fp32 out, fp32 accumulation.  Single-mode launches on plain (no CSR) sources whose channel
+ * Arithmetic: fp32 in, fp32 out, fp32 accumulation.  Single-mode launches on aligned sources whose channel
  *   counts are multiples of 32, with F >= 64, multiply on the bf16 matrix pipe: each fp32 operand is split exactly
  *   into three bf16 pieces and six cross products per multiply-add are accumulated in fp32 -- as accurate as an fp32
  *   FMA chain, not bit-identical to the other kernels' exact-fp32 MFMA, and an inf operand gives
@@ -196,7 +190,7 @@ int cape_gconv_fwd(const cape_src_t *srcs, int32_t nsrc, float *y, int64_t y_sam
  *     multiple of 4; the bound of a row is the maximum over its rowmax_w entries), written by the kernel that produced the
  *     tensor (rowmax_out below and of cape_spmm* / cape_bwd_prep) or by cape_rowmax;
  *   - per weight column: the piece planes and reciprocal scales cape_weight_pieces prepares once per step.
- * Launches whose sources are plain (no CSR), whole 32-channel chunks, 16-byte aligned, with F >= 64 and all of the above
+ * Launches whose sources are whole 32-channel chunks, 16-byte aligned, with F >= 64 and all of the above
  * given take gemm_h2_kernel; everything else is computed as before (the row-bound output works with every kernel).
  */
 typedef struct cape_h2_src {
@@ -258,7 +252,7 @@ int cape_weight_pieces(const cape_wpiece_item_t *dev_items, int32_t nitems, cons
                        const int32_t *dev_planes_off, int32_t planes_blocks, void *stream);
 
 /* Which kernel cape_gconv_fwd would run for these arguments (pure query, no launch):
- * plan[0] = family (0: gather-GEMM gconv_fwd_kernel, 1: pipelined plain-source gemm_plain_kernel, 2: the same on
+ * plan[0] = family (0: generic staging for unaligned or unpadded sources gconv_fwd_kernel, 1: pipelined gemm_plain_kernel, 2: the same on
  * the bf16 pipe with the exact three-way operand split, gemm_split_kernel),
  * plan[1], plan[2] = workgroup tile rows x columns, plan[3] = weight layout of families 1 and 2
  * (1: contraction-contiguous, 0: output-contiguous).  Used by bench.py to attribute per-launch work to
@@ -275,8 +269,8 @@ int cape_rowscale_reduce(const float *dz, int64_t dz_sample_stride, int32_t lddz
                          float *out, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
- * Weight gradient of the fused gather-GEMM:
- *   dW_s[c*w_rs + f*w_cs] (+)= sum_{n,r} A_s[n,r,c] * dz_s[n,r,f]
+ * Weight gradient of the contraction:
+ *   dW_s[c*w_rs + f*w_cs] (+)= sum_{n,r} x_s[n,r,c] * dz_s[n,r,f]
  * for every source s (w is the *output* gradient block here and is written, w2 is ignored).
  * dz_s = dz2 for the sources whose bit is set in dz2_mask (dz2 has the layout of dz), dz otherwise:
  * res_block_affine's two weight blocks contract the same inputs against different gradients (the
@@ -354,7 +348,7 @@ int cape_gconv_dw_batch(const cape_dw_item_t *items, int32_t nitems, void *strea
  * info = {launches, workgroups in all, bytes of kernel arguments per launch, largest grid}. */
 int cape_gconv_dw_batch_plan(const cape_dw_item_t *items, int32_t nitems, int32_t *units, int32_t max_units, int32_t info[4]);
 
-/* Which kernel cape_gconv_dw would run for these arguments (pure query, no launch): plan[0] = family (0: gather form
+/* Which kernel cape_gconv_dw would run for these arguments (pure query, no launch): plan[0] = family (0: generic form
  * gconv_dw_kernel, 1: dw_plain_kernel on the exact-fp32 MFMA, 2: dw_packed_kernel, 3: dw_split_kernel on the bf16 pipe
  * with the exact three-way operand split), plan[1], plan[2] = tile channels x output columns, plan[3] = number of
  * partial slabs the fixed-order reduction sums.  The parity tests use it to prove that every kernel the benchmarked

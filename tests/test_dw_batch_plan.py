@@ -31,7 +31,6 @@ def make_items(shapes, N=16):
         for i, (s, Cn) in enumerate(zip(srcs, Cs)):
             base += 0x1000000
             s.x, s.x_sample_stride, s.ldx, s.C = base, Mo * Cn, Cn, Cn
-            s.rowptr = s.colidx = s.vals = None
             s.w, s.w_rs, s.w_cs = base + 0x800000, F, 1
             s.w2, s.w2_rs, s.w2_cs = None, 0, 0
             h2.src_rowmax[i], h2.src_rowmax_w[i] = base + 0x400000, 4 * -(-Cn // 128)

@@ -138,7 +138,7 @@ def test_bf16_backward_kernels_on_identical_inputs(mesh_ops):
         assert dz.dtype == bf and rel(dz, ref_dz) < 1e-2 and rel(dbv, ref_dz.sum((0, 1))) < 1e-3
         ChP = (Ch + 3) // 4 * 4
         Gall = ops.alloc_act(N, Mo, K * ChP, dev, dtype=bf)
-        ops.gconv_fwd([dict(x=dz, csr=None, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Ch)
+        ops.gconv_fwd([dict(x=dz, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Ch)
         Gref = dz.float() @ W.t()                          # (weights enter as two bf16 planes hi + mid: 16 significant bits)
         Gs = [Gall[:, :, k * ChP:k * ChP + Ch] for k in range(K)]
         for k in range(K):
@@ -156,7 +156,7 @@ def test_bf16_backward_kernels_on_identical_inputs(mesh_ops):
                 ref[n] += S @ Gs[k][n].float()
         assert dx.dtype == bf and tuple(dx.shape) == (N, Mi, Ch) and rel(dx, ref) < 1e-2
         dW = torch.empty((Ch, Fout), device=dev)
-        ops.gconv_dw([dict(x=act_(x), csr=None, w=(dW, 0, Fout, 1))], dz)
+        ops.gconv_dw([dict(x=act_(x), w=(dW, 0, Fout, 1))], dz)
         assert rel(dW, torch.einsum('nrc,nrf->cf', x.float(), dz.float())) < 1e-3
 
 

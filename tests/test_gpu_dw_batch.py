@@ -91,7 +91,7 @@ def _run(case, batch):
                 if t is None:
                     t = hx[id(e["x"])] = _act(e["x"])
                 b = case["blocks"][e["block"]]
-                ent.append(dict(x=t, csr=None, w=(bucket, b["off"], b["F"], 1), use_dz2=e["use2"]))
+                ent.append(dict(x=t, w=(bucket, b["off"], b["F"], 1), use_dz2=e["use2"]))
             ops.gconv_dw(ent, hdz, accumulate=it["acc"], dz2=hdz2, defer=True)
         nbatched = sum(1 for q in ops.DEFERRED_DW if q[5])
         assert len(ops.DEFERRED_DW) == len(case["items"])
@@ -148,7 +148,7 @@ def test_operand_written_between_queue_and_flush_is_refused(case):
             hdz = _act(it["dz"])
             hx = _act(it["ent"][0]["x"])
             dW = torch.zeros((128, 128), device=DEV)
-            ops.gconv_dw([dict(x=hx, csr=None, w=(dW, 0, 128, 1))], hdz, defer=True)
+            ops.gconv_dw([dict(x=hx, w=(dW, 0, 128, 1))], hdz, defer=True)
             assert ops.DEFERRED_DW[-1][5]
             (hdz if victim == "dz" else hx).add_(1)
             with pytest.raises(RuntimeError, match="written in place"):

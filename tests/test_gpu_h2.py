@@ -71,7 +71,7 @@ def test_gemm_h2_forward_planes(case):
     acc = sum(xs[k].astype(np.float64) @ W[k::K].astype(np.float64) for k in range(K))          # rows c*K + k
     entries = []
     for k in range(K):
-        e = dict(x=hx[k], csr=None, w=(hW, k * F, K * F, 1), p=P.fwd(k), rm=ops.rowmax(hx[k]))
+        e = dict(x=hx[k], w=(hW, k * F, K * F, 1), p=P.fwd(k), rm=ops.rowmax(hx[k]))
         if dual and k == 0:
             e["w2"], e["p2"] = (hWa, 0, F, 1), Pa.fwd(0)
         entries.append(e)
@@ -149,7 +149,7 @@ def test_gemm_h2_backward_planes(case):
             hdz = _act(dz)
             ChP = (Ch + 3) // 4 * 4
             G = ops.alloc_act(N, Mo, K * ChP, torch.device(DEV))
-            ops.gconv_fwd([dict(x=hdz, csr=None, w=(hW, 0, 1, Fo), p=(P.b_hi.data_ptr(), P.b_lo.data_ptr(), Fo), rm=ops.rowmax(hdz))], G,
+            ops.gconv_fwd([dict(x=hdz, w=(hW, 0, 1, Fo), p=(P.b_hi.data_ptr(), P.b_lo.data_ptr(), Fo), rm=ops.rowmax(hdz))], G,
                           deinterleave=K, F=K * Ch, wsi=ops._ptr(P.bsi))
             got = G.cpu().numpy().astype(np.float64)
             full = dz.astype(np.float64) @ W.astype(np.float64).T                   # column j = c*K + k
@@ -159,10 +159,10 @@ def test_gemm_h2_backward_planes(case):
         else:
             Ts = [(rng.standard_normal((N, Mo, Fo)) * scales[:, :, None]).astype(np.float32) for _ in range(K + (1 if aff else 0))]
             hT = [_act(t) for t in Ts]
-            ent = [dict(x=hT[k], csr=None, w=(hW, k * Fo, 1, K * Fo), p=P.bwd(k), rm=ops.rowmax(hT[k])) for k in range(K)]
+            ent = [dict(x=hT[k], w=(hW, k * Fo, 1, K * Fo), p=P.bwd(k), rm=ops.rowmax(hT[k])) for k in range(K)]
             want = sum(Ts[k].astype(np.float64) @ W[k::K].astype(np.float64).T for k in range(K))
             if aff:
-                ent.append(dict(x=hT[K], csr=None, w=(hWa, 0, 1, Fo), p=Pa.bwd(0), rm=ops.rowmax(hT[K])))
+                ent.append(dict(x=hT[K], w=(hWa, 0, 1, Fo), p=Pa.bwd(0), rm=ops.rowmax(hT[K])))
                 want = want + Ts[K].astype(np.float64) @ Wa.astype(np.float64).T
                 assert torch.equal(P.bsc, Pa.bsc)                                # the paired tensors share their channel scales
             dx = ops.alloc_act(N, Mo, Ch, torch.device(DEV))
@@ -301,7 +301,7 @@ def test_dw_h2(case):
         hx = _act(x)
         ops.rowmax(hx)
         dW = torch.zeros((C_, F), device=DEV)
-        ent.append(dict(x=hx, csr=None, w=(dW, 0, F, 1)))
+        ent.append(dict(x=hx, w=(dW, 0, F, 1)))
         want.append(np.einsum('nrc,nrf->cf', x.astype(np.float64), dz.astype(np.float64)))
     ops.PLAN_LOG = set()
     try:

@@ -32,14 +32,16 @@ CASES = [  # N, Mi, Mo, [C per source], F, dual, empty_rows
     (2, 129, 129, [36, 36], 70, True, 3),
     (1, 300, 150, [64], 130, False, 0),
     (4, 65, 65, [3, 3, 3], 40, True, 0),
-    (2, 150, 150, [12, 8, 4], 32, False, 2),      # aligned: pipelined kernels, three sources packed into one dW tile
+    (2, 150, 150, [12, 8, 4], 32, False, 2),      # whole float4 columns, F one MFMA tile (the views stay unaligned: ld = C + 9)
     (3, 170, 90, [36, 36], 72, False, 0),
     (2, 140, 140, [68, 132], 136, False, 0),
 ]
 
 
 @pytest.mark.parametrize("case", CASES, ids=lambda c: "N%d_Mi%d_Mo%d_F%d%s" % (c[0], c[1], c[2], c[4], "_dual" if c[5] else ""))
-def test_gather_gemm_ragged(case):
+def test_operator_then_generic_gemm_ragged(case):
+    """What a layer does on sources the aligned kernels cannot take: S x by the streaming sparse kernel, written into a
+    channel-offset, row-padded view, then the contraction and its weight gradient through the generic staging (family 0)."""
     from cape_amd import ops
     from cape_amd.graph import HostCSR
     N, Mi, Mo, Cs, F, dual, empty = case
@@ -47,19 +49,24 @@ def test_gather_gemm_ragged(case):
     rng = np.random.default_rng(Mi * 1000 + F)
     ref = np.zeros((N, Mo, F))
     ref2 = np.zeros((N, Mo, F))
-    entries, keep = [], []
+    entries, keep, As = [], [], []
     for i, C in enumerate(Cs):
         # source 0 is the identity when shapes allow, the others are random operators (some rows empty, one long)
         S = None if (i == 0 and Mi == Mo) else rand_csr(rng, Mo, Mi, 0.05, empty_rows=empty, long_row=min(Mi, 40))
         # activations live inside a wider buffer: a channel-offset, row-padded view
-        buf = torch.zeros(N, Mi, C + 9, device=dev)
+        buf = torch.zeros(N, Mo, C + 9, device=dev)
         x = rng.standard_normal((N, Mi, C))
-        buf[:, :, 5:5 + C] = torch.tensor(x, dtype=torch.float32)
+        hx = torch.tensor(x, dtype=torch.float32, device=dev)
+        if S is None:
+            buf[:, :, 5:5 + C] = hx
+        else:
+            ops.spmm(hx, ops.DeviceCSR(HostCSR(S), dev), y=buf[:, :, 5:5 + C])
         W = rng.standard_normal((C, F)) * 0.3
         hW = torch.tensor(W, dtype=torch.float32, device=dev)
         A = x if S is None else np.stack([S @ x[n] for n in range(N)])
+        As.append(A)
         ref += A @ W
-        e = dict(x=buf[:, :, 5:5 + C], csr=None if S is None else ops.DeviceCSR(HostCSR(S), dev), w=(hW, 0, F, 1))
+        e = dict(x=buf[:, :, 5:5 + C], w=(hW, 0, F, 1))
         if dual and i == 0:
             W2 = rng.standard_normal((C, F)) * 0.3
             hW2 = torch.tensor(W2, dtype=torch.float32, device=dev)
@@ -69,17 +76,26 @@ def test_gather_gemm_ragged(case):
         entries.append(e)
         keep += [buf, hW]
     y = ops.alloc_act(N, Mo, F, dev)
+    ops.PLAN_LOG = set()
+    try:
+        if dual:
+            mask = torch.zeros((N, Mo, (F + 31) // 32), device=dev, dtype=torch.int32)
+            ops.gconv_fwd(entries, y, mask=mask)
+        else:
+            b = rng.standard_normal(F) * 0.1
+            hb = torch.tensor(b, dtype=torch.float32, device=dev)
+            ops.gconv_fwd(entries, y, bias=hb, bias_mode=1, act="leaky")
+        plans = ops.PLAN_LOG
+    finally:
+        ops.PLAN_LOG = None
+    # every source is an unaligned view: the launch takes the generic staging of gconv_fwd_kernel
+    assert len(plans) == 1 and [pl[:2] for pl in plans] == [("fwd", 0)], plans
     if dual:
-        mask = torch.zeros((N, Mo, (F + 31) // 32), device=dev, dtype=torch.int32)
-        ops.gconv_fwd(entries, y, mask=mask)
         want = np.maximum(ref, 0) + ref2
         bits = ((mask.cpu().numpy().astype(np.int64)[..., None] >> np.arange(32)) & 1).reshape(N, Mo, -1)[:, :, :F]
         safe = np.abs(ref) > 1e-4 * np.abs(ref).max()          # sign is only meaningful away from 0
         assert np.array_equal(bits[safe] == 1, (ref > 0)[safe])
     else:
-        b = rng.standard_normal(F) * 0.1
-        hb = torch.tensor(b, dtype=torch.float32, device=dev)
-        ops.gconv_fwd(entries, y, bias=hb, bias_mode=1, act="leaky")
         z = ref + b
         want = np.where(z > 0, z, 0.2 * z)
     torch.cuda.synchronize()
@@ -88,13 +104,15 @@ def test_gather_gemm_ragged(case):
     dz = rng.standard_normal((N, Mo, F))
     hdz = torch.tensor(dz, dtype=torch.float32, device=dev)
     grads = [torch.empty(C, F, device=dev) for C in Cs]
-    ops.gconv_dw([dict(x=e["x"], csr=e["csr"], w=(gw, 0, F, 1)) for e, gw in zip(entries, grads)], hdz)
+    ops.PLAN_LOG = set()
+    try:
+        ops.gconv_dw([dict(x=e["x"], w=(gw, 0, F, 1)) for e, gw in zip(entries, grads)], hdz)
+        plans = ops.PLAN_LOG
+    finally:
+        ops.PLAN_LOG = None
+    assert [pl[:2] for pl in plans] == [("dw", 0)], plans          # likewise gconv_dw_kernel
     torch.cuda.synchronize()
-    for i, (e, gw) in enumerate(zip(entries, grads)):
-        x = e["x"].cpu().numpy().astype(np.float64)
-        S = None if e["csr"] is None else e["csr"]
-        A = x if S is None else np.stack([sp.csr_matrix((S.vals_t.cpu().numpy().astype(np.float64), S.colidx_t.cpu().numpy(),
-                                                         S.rowptr_t.cpu().numpy()), shape=S.shape) @ x[n] for n in range(N)])
+    for i, (A, gw) in enumerate(zip(As, grads)):
         want_w = np.einsum('nrc,nrf->cf', A, dz)
         assert rel(gw.cpu().numpy(), want_w) < TOL, i
 

@@ -44,7 +44,7 @@ def test_split_gemm_ragged(case):
             hW = torch.tensor(np.ascontiguousarray(W.T), dtype=torch.float32, device=dev)      # [F, C]
             w = (hW, 0, 1, C_)
         ref += x.astype(np.float32).astype(np.float64) @ W.astype(np.float32).astype(np.float64)
-        entries.append(dict(x=hx, csr=None, w=w))
+        entries.append(dict(x=hx, w=w))
         keep += [hx, hW]
     bias = None
     if with_bias:

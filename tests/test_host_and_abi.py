@@ -151,9 +151,8 @@ def test_forward_plan_query_is_pure_host_logic():
 
     def srcs(specs):
         arr = (_lib.CapeSrc * len(specs))()
-        for s, (Cn, ldx, gather, w_rs, w_cs, base) in zip(arr, specs):
+        for s, (Cn, ldx, w_rs, w_cs, base) in zip(arr, specs):
             s.x, s.x_sample_stride, s.ldx, s.C = base, 6890 * ldx, ldx, Cn
-            s.rowptr = s.colidx = s.vals = (0x2000 if gather else None)
             s.w, s.w_rs, s.w_cs = 0x10000, w_rs, w_cs
             s.w2, s.w2_rs, s.w2_cs = None, 0, 0
         return arr
@@ -166,30 +165,29 @@ def test_forward_plan_query_is_pure_host_logic():
     split = int(os.environ.get("CAPE_GEMM_BF16X6", "1"))     # bf16x6 family (2) replaces the fp32-MFMA family (1) where eligible
     fam = 2 if split else 1
     # plain aligned sources, forward weight layout (rows c*K+k of [C*K, F], F contiguous) -> pipelined kernel, 64x64
-    assert plan([(64, 64, False, 2 * 128, 1, 0x4000), (64, 64, False, 2 * 128, 1, 0x8000)], 16, 862, 128) == [fam, 64, 64, 0]
+    assert plan([(64, 64, 2 * 128, 1, 0x4000), (64, 64, 2 * 128, 1, 0x8000)], 16, 862, 128) == [fam, 64, 64, 0]
     # data-gradient layout (contraction contiguous)
-    assert plan([(128, 128, False, 1, 2 * 128, 0x4000)], 16, 862, 64) == [fam, 64, 64, 1]
+    assert plan([(128, 128, 1, 2 * 128, 0x4000)], 16, 862, 64) == [fam, 64, 64, 1]
     # wide coarse-level layer: 128x128 tiles for the split family once every CU gets two of them
-    assert plan([(512, 512, False, 512, 1, 0x4000)] * 2, 16, 862, 512) == ([2, 128, 128, 0] if split else [1, 64, 64, 0])
-    assert plan([(512, 512, False, 256, 1, 0x4000)], 16, 862, 256) == [fam, 64, 64, 0]
+    assert plan([(512, 512, 512, 1, 0x4000)] * 2, 16, 862, 512) == ([2, 128, 128, 0] if split else [1, 64, 64, 0])
+    assert plan([(512, 512, 256, 1, 0x4000)], 16, 862, 256) == [fam, 64, 64, 0]
     # a source that is not a whole number of 32-wide chunks, or a second weight set, stays on the fp32-MFMA family
-    assert plan([(48, 48, False, 128, 1, 0x4000)], 16, 862, 128)[0] == 1
+    assert plan([(48, 48, 128, 1, 0x4000)], 16, 862, 128)[0] == 1
     # narrow output -> 128 x 32 tiles
-    assert plan([(64, 64, False, 32, 1, 0x4000)], 16, 6890, 32) == [1, 128, 32, 0]
-    # gathered source, unaligned base, or unpadded odd channel count -> gather kernel
-    assert plan([(64, 64, True, 128, 1, 0x4000)], 16, 862, 128)[0] == 0
-    assert plan([(64, 64, False, 128, 1, 0x4004)], 16, 862, 128)[0] == 0
-    assert plan([(3, 3, False, 64, 1, 0x4000)], 16, 6890, 64)[0] == 0
+    assert plan([(64, 64, 32, 1, 0x4000)], 16, 6890, 32) == [1, 128, 32, 0]
+    # unaligned base, or unpadded odd channel count -> the generic kernel
+    assert plan([(64, 64, 128, 1, 0x4004)], 16, 862, 128)[0] == 0
+    assert plan([(3, 3, 64, 1, 0x4000)], 16, 6890, 64)[0] == 0
     # row-padded 3-channel input: at most 8 input channels in total -> the narrow-input form (csrc/narrow.h), also for two sources;
     # nine channels are one too many
     narrow = int(os.environ.get("CAPE_NARROW", "1"))
-    assert plan([(3, 4, False, 64, 1, 0x4000)], 16, 6890, 64)[0] == (4 if narrow else 1)
-    assert plan([(3, 4, False, 2 * 64, 1, 0x4000), (3, 4, False, 2 * 64, 1, 0x8000)], 16, 6890, 64)[0] == (4 if narrow else 1)
-    assert plan([(3, 4, False, 3 * 64, 1, 0x4000)] * 3, 16, 6890, 64)[0] == 1
+    assert plan([(3, 4, 64, 1, 0x4000)], 16, 6890, 64)[0] == (4 if narrow else 1)
+    assert plan([(3, 4, 2 * 64, 1, 0x4000), (3, 4, 2 * 64, 1, 0x8000)], 16, 6890, 64)[0] == (4 if narrow else 1)
+    assert plan([(3, 4, 3 * 64, 1, 0x4000)] * 3, 16, 6890, 64)[0] == 1
     assert lib.cape_gconv_fwd_plan(None, 1, 16, 862, 128, (C.c_int32 * 4)()) == -1
     # weight-gradient workspace: positive, grows with the output size, argument errors reported
-    w1 = lib.cape_gconv_dw_workspace_bytes(srcs([(64, 64, False, 64, 1, 0x4000)]), 1, 16, 862, 64)
-    w2 = lib.cape_gconv_dw_workspace_bytes(srcs([(512, 512, False, 512, 1, 0x4000)] * 2), 2, 16, 862, 512)
+    w1 = lib.cape_gconv_dw_workspace_bytes(srcs([(64, 64, 64, 1, 0x4000)]), 1, 16, 862, 64)
+    w2 = lib.cape_gconv_dw_workspace_bytes(srcs([(512, 512, 512, 1, 0x4000)] * 2), 2, 16, 862, 512)
     assert 0 < w1 < w2 and lib.cape_gconv_dw_workspace_bytes(None, 1, 16, 862, 64) == -1
 
 
@@ -206,7 +204,6 @@ def test_weight_gradient_split_plan_is_one_balanced_round():
         arr = (_lib.CapeSrc * len(Cs))()
         for i, (s, Cn) in enumerate(zip(arr, Cs)):
             s.x, s.x_sample_stride, s.ldx, s.C = 0x100000 * (i + 1), Mo * Cn, Cn, Cn
-            s.rowptr = s.colidx = s.vals = None
             s.w, s.w_rs, s.w_cs = 0x10000000, 512, 1
             s.w2, s.w2_rs, s.w2_cs = None, 0, 0
         return arr

@@ -6,7 +6,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from cape_amd import ops
 from cape_amd.graph import ConvOperators
 from cape_amd.load_data import load_graph_mtx
-from tools.bench_gconv import timeit
+from tools.gpu_timeit import timeit
 
 L, D, U, p, Ld, Dd, Ud = load_graph_mtx(None, True)
 dev = torch.device('cuda:0')

@@ -30,13 +30,13 @@ for name, N, Mo, Cs, F, dual, kc in CASES:
         W = 0.1 * torch.randn(F, Ktot, device=dev)
         ent, off = [], 0
         for x, c in zip(xs, Cs):
-            ent.append(dict(x=x, csr=None, w=(W, off, 1, Ktot)))
+            ent.append(dict(x=x, w=(W, off, 1, Ktot)))
             off += c
     else:
         W = 0.1 * torch.randn(Ktot, F, device=dev)
         ent, off = [], 0
         for x, c in zip(xs, Cs):
-            ent.append(dict(x=x, csr=None, w=(W, off * F, F, 1)))
+            ent.append(dict(x=x, w=(W, off * F, F, 1)))
             off += c
     mask = None
     if dual:

@@ -8,7 +8,7 @@ sys.path.insert(0, '.')
 from cape_amd import ops
 from cape_amd.graph import ConvOperators
 from cape_amd.load_data import load_graph_mtx
-from tools.bench_gconv import timeit
+from tools.gpu_timeit import timeit
 
 L, D, U, p, Ld, Dd, Ud = load_graph_mtx(None, True)
 dev = torch.device('cuda:0')

@@ -41,7 +41,7 @@ def main():
         # 2. G = dz W^T de-interleaved
         ChP = (Ch + 3) // 4 * 4
         Gall = ops.alloc_act(N, Mo, K * ChP, dev, dtype=dt)
-        ops.gconv_fwd([dict(x=dz, csr=None, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Ch)
+        ops.gconv_fwd([dict(x=dz, w=(W, 0, 1, Fout))], Gall, deinterleave=K, F=K * Ch)
         Gref = dz.float() @ W.t()                 # [N, Mo, Ch*K], column c*K + k
         for k in range(K):
             print("  G_%d" % k, rel(Gall[:, :, k * ChP:k * ChP + Ch], Gref[:, :, k::K]))
@@ -69,7 +69,7 @@ def main():
         x = torch.randn((N, Mo, Ch), generator=g).to(dev).to(dt)
         xa = ops.alloc_act(N, Mo, Ch, dev, dtype=dt); xa.copy_(x)
         dW = torch.empty((Ch, Fout), device=dev)
-        ops.gconv_dw([dict(x=xa, csr=None, w=(dW, 0, Fout, 1))], dz)
+        ops.gconv_dw([dict(x=xa, w=(dW, 0, Fout, 1))], dz)
         print("dW", rel(dW, torch.einsum('nrc,nrf->cf', x.float(), dz.float())))
 
 

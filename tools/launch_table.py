@@ -1,4 +1,4 @@
-"""Per-launch table of the gather-GEMM launches of one training step (HIP-event timed, eager)."""
+"""Per-launch table of the contraction launches of one training step (HIP-event timed, eager)."""
 import sys, torch
 sys.path.insert(0, '.')
 import bench
@@ -14,7 +14,7 @@ for _ in range(2):
 orig = ops.gconv_fwd
 def wrapped(entries, y, **kw):
     N, Mo, F = y.shape
-    desc = "Mo%5d F%4d src[%s]%s" % (Mo, F, ",".join("%d%s" % (int(e.get("C", e["x"].shape[2])), "g" if (e.get("csr") is not None and not e["csr"].identity) else "") for e in entries), " dual" if any(e.get("w2") is not None for e in entries) else "")
+    desc = "Mo%5d F%4d src[%s]%s" % (Mo, F, ",".join("%d" % int(e.get("C", e["x"].shape[2])) for e in entries), " dual" if any(e.get("w2") is not None for e in entries) else "")
     ops._last_desc = desc
     if "rep" in sys.argv and ops.LAUNCH_LOG is not None:
         for _ in range(2):

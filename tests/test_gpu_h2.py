@@ -1,12 +1,21 @@
-"""The fp16 two-piece contractions (cape_amd/csrc/gemm_h2.h, pieces.hip) through the C-ABI, against float64 numpy:
+"""The fp16 two-piece contractions (cape_amd/csrc/gemm_h2.h, gemm_h2x.h, pieces.hip) through the C-ABI, against float64 numpy.
 
-* gemm_h2_kernel in every tile form (128 x 128, 64 x 64, DUAL 128 x 64; the library must report plan family 3): ragged row / column
-  counts, several sources, forward and data-gradient plane layouts, the de-interleaving epilogue, rank-1 terms, rows spanning
-  40 binades incl. a zero row, a 1e-30 row and a 6e4 row -- every row judged on its OWN norm (the scales are per row);
+This file holds the model's own shapes and the producers around the kernels; every case asserts the FULL plan tuple the
+library reports (family, tile, layout, DUAL):
+
+* gemm_h2_kernel<64, 64>, the DUAL 128 x 64 form (with its ReLU sign mask) and gemm_h2x_kernel (the wide 128 x 256 tile) on the
+  forward and data-gradient plane layouts, the de-interleaving epilogue, rows spanning 40 binades incl. a zero row, a 1e-30 row
+  and a 6e4 row -- every row judged on its OWN norm (the scales are per row); two short shapes that must stay on the
+  six-product kernel (family 2);
 * the row bounds every producer writes (GEMM epilogues, sparse kernels, backward-prep, standalone pass): they must bound the
   true maxima and stay within the documented slack;
 * the weight piece planes against their numpy restatement (tests/test_h2_numerics.py);
-* dw_h2_kernel (plan family 4) on ragged shapes.
+* dw_h2_kernel (plan family 4) on ragged shapes: the 64 x 128 and 128 x 128 tiles.
+
+tests/test_gpu_h2_tiles.py (cases, references and judges in tests/h2_cases.py) holds every OTHER tile form and the kernels' edge
+paths: 128 x 128, 128 x 64 and 64 x 128 single, every pipeline length, the general epilogue (rank-1 terms, vertex bias, tanh),
+bounds of width 8 / 12 / 16 / 20 written by a producing epilogue, channel-offset views next to NaN, and the 64 x 64 / 128 x 64
+weight-gradient tiles, dz2, accumulate and row ranges shorter than a chunk.
 """
 import ctypes as C
 
@@ -14,50 +23,28 @@ import numpy as np
 import pytest
 import torch
 
+from tests.h2_cases import _act, _per_row_err, _row_scales, judge_mask, judge_rm
 from tests.test_h2_numerics import scale_of, split2
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 
 
-def _act(a):
-    from cape_amd import ops
-    t = ops.alloc_act(a.shape[0], a.shape[1], a.shape[2], torch.device(DEV))
-    t.copy_(torch.tensor(a, dtype=torch.float32))
-    return t
-
-
-def _row_scales(N, M, rng):
-    s = 2.0 ** (-rng.integers(0, 24, (N, M))).astype(np.float64)
-    s[0, min(3, M - 1)] = 0.0
-    s[0, min(5, M - 1)] = 1e-30
-    s[-1, min(7, M - 1)] = 6e4
-    return s
-
-
-def _per_row_err(got, want):
-    """largest relative L2 error of a row judged on that row's own norm (rows that are exactly zero must be exactly zero)."""
-    n = np.sqrt((want ** 2).sum(-1))
-    e = np.sqrt(((got - want) ** 2).sum(-1))
-    assert np.all(e[n == 0] == 0)
-    return float((e[n > 0] / n[n > 0]).max())
-
-
-FWD_CASES = [  # N, Mo, Ch, K, F, affine(DUAL), act, bias
-    (2, 203, 128, 2, 72, False, 'leaky', True),       # 64 x 64 tiles, ragged everything
-    (2, 203, 64, 2, 72, False, 'leaky', True),        # 128 contraction indices into 72 columns: short -> six-product kernel
-    (16, 1000, 256, 2, 512, False, None, False),       # 128 x 128 tiles (16*8*4 = 512), 16 chunks
-    (16, 300, 256, 1, 128, False, 'relu', True),       # K total 256: 64 x 64 tiles
-    (3, 257, 128, 2, 96, True, None, False),           # DUAL 128 x 64
-    (16, 862, 512, 2, 256, True, None, False),         # DUAL at the model's widest affine block
-    (1, 37, 32, 3, 64, False, None, False),            # short: 3 chunks of 32 -> stays on the six-product kernel (family 2)
+FWD_CASES = [  # N, Mo, Ch, K, F, affine(DUAL), act, bias, expected plan (family, BM, BN, layout)
+    (2, 203, 128, 2, 72, False, 'leaky', True, (3, 64, 64, 1)),       # 64 x 64 tiles, ragged everything
+    (2, 203, 64, 2, 72, False, 'leaky', True, (2, 64, 64, 0)),        # 128 contraction indices into 72 columns: short -> six-product kernel
+    (16, 1000, 256, 2, 512, False, None, False, (3, 128, 256, 1)),     # wide 128 x 256 tiles (16*8*2 = 256 of them, Ktot = 512): gemm_h2x_kernel, 16 chunks
+    (16, 300, 256, 1, 128, False, 'relu', True, (3, 64, 64, 1)),       # K total 256, 48 tiles of 128 x 128: 64 x 64 tiles
+    (3, 257, 128, 2, 96, True, None, False, (3, 128, 64, 1)),          # DUAL 128 x 64
+    (16, 862, 512, 2, 256, True, None, False, (3, 128, 64, 1)),        # DUAL at the model's widest affine block
+    (1, 37, 32, 3, 64, False, None, False, (2, 64, 64, 0)),            # short: 3 chunks of 32 -> stays on the six-product kernel (family 2)
 ]
 
 
 @pytest.mark.parametrize("case", FWD_CASES, ids=lambda c: "N%d_Mo%d_C%dx%d_F%d%s" % (c[0], c[1], c[2], c[3], c[4], "_dual" if c[5] else ""))
 def test_gemm_h2_forward_planes(case):
     from cape_amd import _lib, ops
-    N, Mo, Ch, K, F, dual, act, with_bias = case
+    N, Mo, Ch, K, F, dual, act, with_bias, plan = case
     rng = np.random.default_rng(Mo + F)
     W = (rng.standard_normal((Ch * K, F)) * 0.3 * 2.0 ** (-rng.integers(0, 12, (1, F)))).astype(np.float32)      # columns of different size
     Wa = (rng.standard_normal((Ch, F)) * 0.2).astype(np.float32) if dual else None
@@ -87,7 +74,7 @@ def test_gemm_h2_forward_planes(case):
         want = np.where(want > 0, want, 0.2 * want) if act == 'leaky' else np.maximum(want, 0) if act == 'relu' else want
     y = ops.alloc_act(N, Mo, F, torch.device(DEV))
     rm_y = ops.alloc_rm(y)
-    mask = torch.empty((N, Mo, (F + 31) // 32), device=DEV, dtype=torch.int32) if dual else None
+    mask = torch.full((N, Mo, (F + 31) // 32), 0x5A5A5A5A, device=DEV, dtype=torch.int32) if dual else None
     ops.PLAN_LOG = set()
     try:
         ops.gconv_fwd(entries, y, bias=bias, bias_mode=_lib.BIAS_CHANNEL, act=act or "none", mask=mask, wsi=ops._ptr(P.fsi),
@@ -97,8 +84,8 @@ def test_gemm_h2_forward_planes(case):
         ops.PLAN_LOG = None
     # (csrc/gemm_h2.h h2_eligible: short contractions are latency-bound launches and stay on the six-product kernel)
     h2 = Ch * K >= 256 or (Ch * K >= 128 and F >= 128)
-    fam = {p[1] for p in plans if p[0] == "fwd"}
-    assert fam == ({3} if h2 else {2}), plans
+    assert (plan[0] == 3) == h2
+    assert plans == {("fwd",) + plan + (int(dual),)}, plans
     got = y.cpu().numpy().astype(np.float64)
     if with_bias and not dual:
         # the bias is not scaled with the row: judge those rows on the tensor's scale like the other kernels' tests
@@ -106,26 +93,19 @@ def test_gemm_h2_forward_planes(case):
     else:
         err = _per_row_err(got, want)
     assert err < 2e-6, err
+    if dual:
+        # the ReLU sign mask: the sign of accumulator 1, judged where it is not within rounding of zero (tests/h2_cases.py)
+        vscale = sum(np.abs(xs[k].astype(np.float64)) @ np.abs(W[k::K].astype(np.float64)) for k in range(K))
+        judge_mask(acc, vscale, mask.cpu().numpy(), F)
     # the epilogue's row bounds: >= the true maximum of every 32-column block, <= the maximum over the block's four-row group
-    rm = rm_y.cpu().numpy()
-    nb = (F + 31) // 32
-    a = np.abs(y.cpu().numpy())
-    for j in range(nb):
-        blk = a[:, :, 32 * j:32 * j + 32].max(-1)
-        assert np.all(rm[:, :, j] >= blk)
-        Mp = (Mo + 3) // 4 * 4
-        grp = np.zeros((N, Mp))
-        grp[:, :Mo] = blk
-        grp = np.repeat(grp.reshape(N, Mp // 4, 4).max(-1), 4, axis=1)[:, :Mo]
-        assert np.all(rm[:, :, j] <= grp)
-    assert np.all(rm[:, :, nb:] == 0)
+    judge_rm(rm_y.cpu().numpy(), y.cpu().numpy(), F)
 
 
-BWD_CASES = [  # N, Mo, Ch, K, Fout, form: 'deint' = one launch for all orders, 'multi' = one source per order (+ affine term)
-    (4, 431, 128, 2, 256, 'deint', False),
-    (16, 862, 256, 2, 512, 'deint', False),
-    (2, 300, 128, 2, 128, 'multi', True),
-    (16, 1723, 128, 2, 128, 'multi', True),
+BWD_CASES = [  # N, Mo, Ch, K, Fout, form: 'deint' = one launch for all orders, 'multi' = one source per order (+ affine term); tile
+    (4, 431, 128, 2, 256, 'deint', False, (64, 64)),
+    (16, 862, 256, 2, 512, 'deint', False, (128, 256)),           # 16*7*2 = 224 wide tiles: gemm_h2x_kernel
+    (2, 300, 128, 2, 128, 'multi', True, (64, 64)),
+    (16, 1723, 128, 2, 128, 'multi', True, (64, 64)),
 ]
 
 
@@ -133,7 +113,7 @@ BWD_CASES = [  # N, Mo, Ch, K, Fout, form: 'deint' = one launch for all orders, 
 def test_gemm_h2_backward_planes(case):
     """Data gradient: contraction over the Fout columns; output column c (de-interleaved launch: c*K + k)."""
     from cape_amd import ops
-    N, Mo, Ch, K, Fo, form, aff = case
+    N, Mo, Ch, K, Fo, form, aff, tile = case
     rng = np.random.default_rng(Mo + Fo + K)
     W = (rng.standard_normal((Ch * K, Fo)) * 0.3 * 2.0 ** (-rng.integers(0, 10, (Ch, 1)).repeat(K, 0))).astype(np.float32)
     Wa = (rng.standard_normal((Ch, Fo)) * 0.2).astype(np.float32) if aff else None
@@ -171,7 +151,7 @@ def test_gemm_h2_backward_planes(case):
         plans = set(ops.PLAN_LOG)
     finally:
         ops.PLAN_LOG = None
-    assert {p[1] for p in plans if p[0] == "fwd"} == {3}, plans
+    assert plans == {("fwd", 3, tile[0], tile[1], 1, 0)}, plans
     assert _per_row_err(got, want) < 2e-6
 
 
@@ -282,13 +262,14 @@ def test_group_norm_bounds_its_rows(Cn):
         x.grad = None
 
 
-DW_CASES = [(2, 203, [64], 72), (16, 862, [256, 256], 512), (5, 330, [128, 64], 132), (16, 1723, [128, 128], 128)]
+DW_CASES = [(2, 203, [64], 72, (64, 128)), (16, 862, [256, 256], 512, (128, 128)), (5, 330, [128, 64], 132, (128, 128)),
+            (16, 1723, [128, 128], 128, (128, 128))]            # (the other tiles: tests/test_gpu_h2_tiles.py)
 
 
 @pytest.mark.parametrize("case", DW_CASES, ids=lambda c: "N%d_Mo%d_C%s_F%d" % (c[0], c[1], "+".join(map(str, c[2])), c[3]))
 def test_dw_h2(case):
     from cape_amd import ops
-    N, Mo, Cs, F = case
+    N, Mo, Cs, F, tile = case
     rng = np.random.default_rng(Mo + F)
     # rows of very different size inside every workgroup's range: the slab-uniform scales must cope
     sc = 2.0 ** (-rng.integers(0, 12, (N, Mo, 1))).astype(np.float64)
@@ -309,7 +290,7 @@ def test_dw_h2(case):
         plans = set(ops.PLAN_LOG)
     finally:
         ops.PLAN_LOG = None
-    assert {p[1] for p in plans if p[0] == "dw"} == {4}, plans
+    assert plans == {("dw", 4) + tile}, plans
     for e, w in zip(ent, want):
         got = e["w"][0].cpu().numpy().astype(np.float64)
         assert np.abs(got - w).max() / np.abs(w).max() < 2e-6

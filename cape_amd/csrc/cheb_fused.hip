@@ -688,6 +688,8 @@ extern "C" int cape_cheb_fused_bwd(const float *x, int64_t x_sample_stride, int3
     if (!x || !dy || !W || (!dx && !dW) || !workspace || ldx < Cin || lddy < Fout || (dx && lddx < Cin) ||
         !cf_aligned(x, x_sample_stride, ldx) || (dx && !cf_aligned(dx, dx_sample_stride, lddx)) || (reinterpret_cast<uintptr_t>(dW) & 15))
         return CAPE_EINVAL;
+    // the data-gradient kernel reads the rows of dy and copies W to LDS with 16-byte loads
+    if (!cf_aligned(dy, dy_sample_stride, lddy) || (reinterpret_cast<uintptr_t>(W) & 15)) return CAPE_EINVAL;
     if (workspace_bytes < cape_cheb_fused_bwd_workspace_bytes(N, Cin, Fout, K, P)) return CAPE_EWORKSPACE;
     p.x = x; p.xs = x_sample_stride; p.ldx = ldx; p.W = W;
     p.dy = dy; p.dys = dy_sample_stride; p.lddy = lddy;

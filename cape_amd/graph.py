@@ -257,6 +257,10 @@ class ChebPatchPlan(object):
         for nparts in (4, 6, 8, 12, 16, 20, 24, 32, 40, 48, 64, 96, 128):
             if -(-M // nparts) > self.MAX_OWN:
                 continue
+            if M < nparts:
+                # the bisection (cut = round(len * k1 / k)) keeps every part non-empty exactly when the graph has at least
+                # as many vertices as parts; an empty patch (R_0 = R_{K-1} = 0) would make the kernels index vid[-1]
+                continue
             cand = self._build(Lt, A, K, nparts)
             if cand["rmax"] <= rmax_allowed:
                 plan = cand

@@ -158,8 +158,10 @@ class DeviceCSR(object):
             check(rc, "cape_csr_validate")
         # identity operators still keep real arrays for the standalone spmm path
         self.rowptr_t = torch.from_numpy(host.rowptr).to(device)
-        self.colidx_t = torch.from_numpy(host.colidx).to(device)
-        self.vals_t = torch.from_numpy(host.vals).to(device)
+        # (an operator without entries -- L~ of a graph without edges -- keeps one unused slot: the entries refuse NULL arrays,
+        # and with every row empty no kernel reads past the row pointers)
+        self.colidx_t = torch.from_numpy(host.colidx if host.nnz else np.zeros(1, np.int32)).to(device)
+        self.vals_t = torch.from_numpy(host.vals if host.nnz else np.zeros(1, np.float32)).to(device)
         # ELL form for the streaming sparse kernels (None when the operator does not qualify)
         self.ell_w, self.ell_col_t, self.ell_val_t = 0, None, None
         ell = ell_arrays(host)

@@ -846,6 +846,11 @@ int cape_colsum_vertex_bf16(const void *x, int64_t x_sample_stride, int32_t ldx,
  * recurrence for dW = sum_n sum_k T_k(L~) x[n]^T dy[n] (per-workgroup partials in ``workspace``, reduced in a fixed order)
  * and evaluates dx[n] = sum_k T_k(L~) dy[n] W_k^T by Clenshaw's recurrence.  Deterministic, no atomics.  Either of dx / dW
  * may be NULL: that half is skipped (a data-gradient-only sweep through the layer; an input that needs no gradient).
+ * Alignment of the backward entry: like x and dx, dy is read in 16-byte pieces -- its pointer must be 16-byte aligned and
+ * dy_sample_stride and lddy multiples of 4 -- and so is W (16-byte aligned pointer, dense [Cin*K, Fout]); dW is written in
+ * 16-byte pieces.  Anything else returns CAPE_EINVAL before a launch.  (The forward entry reads W and writes y by element:
+ * only x carries the requirement there.)  Every patch of the plan must be non-empty ([3] >= 1): ChebPatchPlan offers no
+ * plan with more patches than vertices.
  */
 int cape_cheb_fused_supported(int32_t Cin, int32_t Fout, int32_t K);
 int cape_cheb_fused_fwd(const float *x, int64_t x_sample_stride, int32_t ldx, const float *W, float *y,

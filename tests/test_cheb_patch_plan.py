@@ -6,57 +6,7 @@ lib/models.py:69-103 and its gradients."""
 import numpy as np
 import scipy.sparse as sp
 
-
-def _emulate(plan, x, W, dy, K, Cin, Fout):
-    """Per-patch evaluation exactly as the kernel organises it (float64)."""
-    M = plan.M
-    y = np.zeros((M, Fout))
-    dx = np.zeros((M, Cin))
-    dW = np.zeros((Cin * K, Fout))
-    Wk = [W[k::K] for k in range(K)]                      # W_k [Cin, Fout]: rows c*K + k
-    for p in range(plan.P):
-        v0, e0 = int(plan.pinfo[p, 0]), int(plan.pinfo[p, 2])
-        r0 = int(plan.csr_rowptr_off[p])
-        R = [int(v) for v in plan.pinfo[p, 3:3 + K]]
-        vid = plan.vid[v0:v0 + R[-1]]
-        nrow = R[max(K - 2, 0)]
-        rp = plan.rowptr[r0:r0 + nrow + 1]
-        A = sp.csr_matrix((plan.val[e0:e0 + rp[-1]].astype(np.float64), plan.lcol[e0:e0 + rp[-1]], rp), shape=(nrow, R[-1]))
-        # the ELL rows the kernel reads describe the same matrix (padding = (own row, 0))
-        er = int(plan.pinfo[p, 1])
-        ec, ev = plan.ell_col[er:er + nrow], plan.ell_val[er:er + nrow]
-        E = sp.csr_matrix((ev.ravel().astype(np.float64), (np.repeat(np.arange(nrow), ec.shape[1]), ec.ravel())), shape=(nrow, R[-1]))
-        assert abs(E - A).max() == 0.0 and plan.ell_col.shape[1] == 12
-        own = R[0]
-        # forward (and the recomputation of the backward's part 1)
-        prev, other = x[vid].copy(), np.full((R[-1], Cin), np.nan)
-        acc = prev[:own] @ Wk[0]
-        dW[0::K] += prev[:own].T @ dy[vid[:own]]
-        for k in range(1, K):
-            Rk = R[K - 1 - k]
-            new = (A[:Rk] @ prev) * (1.0 if k == 1 else 2.0) - (other[:Rk] if k > 1 else 0.0)
-            other[:Rk] = new                                 # in place over T_{k-2}; rows beyond keep stale data
-            prev, other = other, prev
-            assert not np.isnan(prev[:Rk]).any()
-            acc += prev[:own] @ Wk[k]
-            dW[k::K] += prev[:own].T @ dy[vid[:own]]
-        y[vid[:own]] = acc
-        # adjoint by Clenshaw: b_k = G_k + 2 L b_{k+1} - b_{k+2} on the k-ring
-        G = lambda k, Rk: dy[vid[:Rk]] @ Wk[k].T
-        if K == 1:
-            dx[vid[:own]] = G(0, own)
-            continue
-        bA, bB = np.full((R[-1], Cin), np.nan), np.full((R[-1], Cin), np.nan)
-        bA[:R[K - 1]] = G(K - 1, R[K - 1])
-        for k in range(K - 2, 0, -1):
-            Rk = R[k]
-            bB[:Rk] = G(k, Rk) - (bB[:Rk] if k < K - 2 else 0.0)
-            bB[:Rk] += 2.0 * (A[:Rk] @ np.nan_to_num(bA))     # (columns outside the (k+1)-ring are never referenced)
-            assert not np.isnan(A[:Rk] @ np.where(np.isnan(bA), np.inf, bA)).any()
-            bA, bB = bB, bA
-        t = G(0, own) - (bB[:own] if K > 2 else 0.0)
-        dx[vid[:own]] = A[:own] @ np.nan_to_num(bA) + t
-    return y, dx, dW
+from cheb_synth import emulate as _emulate      # shared with tests/test_cheb_synth_host.py
 
 
 def test_patch_plan_and_patch_local_algorithm(mesh_ops):

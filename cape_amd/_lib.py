@@ -213,6 +213,11 @@ SIGNATURES = {
     "cape_smpl_jreg_bwd": (C.c_int, [_p, _i64, _p, _p, _p, _p, _i32, _i32, _i32, _i32, _p, _i64, _p]),
     "cape_smpl_dress_bwd": (C.c_int, [_p, _i64, _p, _p, _p, _i64, _i32, _i32, _p]),
     "cape_smpl_weighted_l2": (C.c_int, [_p, _i64, _p, _i64, _p, _f32, _i32, _i32, _p, _p, _i64, _p]),
+    "cape_smpl_unpose_workspace_bytes": (C.c_int64, [_i32, _i32]),
+    "cape_smpl_unpose_joints": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i32, _p, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _i64,
+                                          _p, _p, _p, _p, _p, _p]),
+    "cape_smpl_unpose_skin": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p, _p]),
+    "cape_smpl_undress": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
 }
 
 # bf16-storage variants with the argument list of their fp32 namesake (include/cape_hip.h, last section)

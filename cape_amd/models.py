@@ -1701,6 +1701,49 @@ class CAPE(base_model):
                 clothed.append(T.cpu().numpy())
         return np.concatenate(posed, 0), np.concatenate(clothed, 0)
 
+    def encode_posed(self, posed, pose, cond, cond2, body_model, mean, std, clothing_idx=None, minimal_shape=None, transl=None,
+                     betas=None, joints_from=None, return_disp=False):
+        """``decode_posed`` the other way: posed registrations in SMPL topology -> what ``encode`` returns.  Per padded batch on
+        the device: ``SMPL.unpose`` (demos.py's posing step inverted) -> ``undress`` (``v_cano - minimal`` of the reference's
+        lib/prep_data.py:74, masked and normalised) -> encoder.  ``posed`` [size, V, 3]; ``pose`` / ``transl`` / ``body_model``
+        / ``mean`` / ``std`` / ``minimal_shape`` as in ``decode_posed``, ``clothing_idx=None``: every vertex; ``betas``
+        [1 or size, <=B] or None; ``joints_from`` [1 or size, V, 3] as in ``SMPL.unpose`` (None: the exact inverse);
+        ``cond`` / ``cond2`` as ``encode`` takes them.  Batching and padding are encode's.  Returns (z_mean, z_logvar, y, y2),
+        and with ``return_disp`` the normalised displacements [size, V, 3] the encoder saw as a fifth."""
+        posed = np.asarray(posed, dtype=np.float32)
+        size = posed.shape[0]
+        body, pose, transl, dressing, _, _ = self._posed_arguments(size, body_model, pose, transl,
+                                                                   (mean, std, clothing_idx, minimal_shape))
+        if posed.shape != (size, body.V, 3):
+            raise ValueError("posed: [size, %d, 3] expected, got %s" % (body.V, posed.shape))
+
+        def rows(name, a, tail):
+            a = np.asarray(a, dtype=np.float32).reshape((-1,) + tail)
+            if a.shape[0] not in (1, size):
+                raise ValueError("%s: %d rows for %d samples" % (name, a.shape[0], size))
+            return a
+
+        betas = None if betas is None else rows("betas", betas, (np.asarray(betas).shape[-1],))
+        jf = None if joints_from is None else rows("joints_from", joints_from, (body.V, 3))
+        jf_all = self._dev(jf) if jf is not None and jf.shape[0] == 1 else None          # one body for every sample: uploaded once
+        self._open_pass()
+        zs, disps = [], []
+        with torch.no_grad():
+            for begin, end, y, y2 in self._embedded(size, cond, cond2):
+                nb = end - begin
+                part = lambda a: None if a is None else self._padded(a, begin, end)[:nb]
+                T, _ = body.unpose(part(posed), part(pose), part(betas), part(transl),
+                                   joints_from=jf_all if jf_all is not None else part(jf))
+                x = torch.zeros((self.batch_size, body.V, 3), dtype=torch.float32, device=self.device)   # encode's zero padding
+                dressing.undress(T, out=x[:nb])
+                with self.variable_scope('generator'):
+                    zm, zv = self.encoder(x, y, y2, use_res_block=self.use_res_block, use_cond=self.cond_encoder)
+                zs.append([t[:nb].cpu().numpy() for t in (zm, zv, y, y2)])
+                if return_disp:
+                    disps.append(x[:nb].cpu().numpy())
+        res = tuple(np.concatenate(l, 0) for l in zip(*zs))
+        return res + (np.concatenate(disps, 0),) if return_disp else res
+
     def fit_posed(self, target, pose, cond, cond2, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None, z0=None,
                   weights=None, steps=200, lr=0.1, lambda_z=0.0, lambda_edge=0.0, optimize_pose=False, optimize_transl=False):
         """The latent codes that explain posed meshes: gradient descent (Adam) on ``z`` through

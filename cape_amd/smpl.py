@@ -6,7 +6,10 @@ bodies (reference demos.py:155-161, 207-213 and :249-331, which go through ``smp
   SMPL.forward_diff(...)     the same as an autograd function: gradients to the rest body, pose, betas and translation
                              (cape_smpl_skin_bwd / cape_smpl_joints_bwd / cape_smpl_jreg_bwd)
   SMPL.pose(...)             the same on numpy arrays
+  SMPL.unpose(...)           the inverse of ``forward``: posed vertices + pose -> the rest body and its joints
+                             (cape_smpl_unpose_joints / cape_smpl_unpose_skin); ``unpose_np`` on numpy arrays
   dress(...)                 de-normalise + clothing mask + minimal body (cape_smpl_dress)
+  undress(...)               its right-inverse: rest body -> normalised displacements (cape_smpl_undress)
   dress_diff(...)            the same with a gradient to the displacements (cape_smpl_dress_bwd)
   weighted_l2(...)           per-sample weighted squared distance to target meshes and its gradient (cape_smpl_weighted_l2)
   create(...), body_models   an ``smplx``-compatible factory: with a one-line ``smplx.py`` in the reference checkout
@@ -129,6 +132,8 @@ class SMPL(object):
         # [shapedirs | posedirs] planar [K][3][V]: lanes of a wave load consecutive words of one coefficient's plane
         basis = np.concatenate([m["shapedirs"].transpose(2, 1, 0), m["posedirs"].transpose(2, 1, 0)], 0)
         jsd = np.einsum("jv,vcb->bjc", jreg.toarray(), m["shapedirs"])          # J_regressor . shapedirs, [B][J][3]
+        # J_regressor . posedirs, [9(J-1)][J][3]: the pose blend's share of the regressed joints, which unposing takes out
+        jpd = np.asarray(jreg @ m["posedirs"].reshape(V, -1)).reshape(J, 3, 9 * (J - 1)).transpose(2, 0, 1)
         # the regressor's transpose for the backward's gather per vertex: CSC of [J, V] = CSR of [V, J]
         jt = jreg.T.tocsr()
         jt.sort_indices()
@@ -137,7 +142,7 @@ class SMPL(object):
                                               ti.ctypes.data_as(C.c_void_p)), "SMPL J_regressor (transposed)")
         self.layouts = dict(rowptr=(rp, np.int32), colidx=(ci, np.int32), vals=(jreg.data, np.float32),
                             ell_j=(ell_j, np.int32), ell_w=(ell_w, np.float32), basis=(basis, np.float32),
-                            jshapedirs=(jsd, np.float32), v_template=(m["v_template"], np.float32),
+                            jshapedirs=(jsd, np.float32), jposedirs=(jpd, np.float32), v_template=(m["v_template"], np.float32),
                             jt_colptr=(tp, np.int32), jt_rowidx=(ti, np.int32), jt_vals=(jt.data, np.float32))
         self._dev = None
         self._parents_c = (C.c_int32 * J)(*[int(x) for x in self.parents])
@@ -205,7 +210,18 @@ class SMPL(object):
                                              self._parents_c, J, V, N, _p(coef), _p(G), _p(jo), _stream()), "cape_smpl_joints")
         return coef, G
 
-    def _launch(self, verts, pose, betas, transl, out):
+    def _body_argument(self, name, t, N):
+        """The checks ``_arguments`` makes on ``verts``, for another body of the call (``joints_from``)."""
+        d = self._upload()
+        if t.requires_grad:
+            raise RuntimeError("cape_amd.smpl: forward only, %s requires grad" % name)
+        if t.dtype != torch.float32 or t.device != d.device or not t.is_contiguous():
+            raise ValueError("cape_amd.smpl: %s must be a contiguous float32 tensor on %s" % (name, d.device))
+        if t.dim() != 3 or t.shape[1:] != (self.V, 3) or t.shape[0] not in (1, N):
+            raise ValueError("%s: [%d or 1, %d, 3] expected, got %s" % (name, N, self.V, tuple(t.shape)))
+        return t
+
+    def _launch(self, verts, pose, betas, transl, out, joints_from=None):
         J, V, d, N = self.J, self.V, self._dev, pose.shape[0]
         if out is None:
             out = (torch.empty((N, V, 3), dtype=torch.float32, device=d.device),
@@ -213,23 +229,91 @@ class SMPL(object):
         vo, jo = out
         if tuple(vo.shape) != (N, V, 3) or tuple(jo.shape) != (N, J, 3) or not (vo.is_contiguous() and jo.is_contiguous()):
             raise ValueError("out: contiguous [N,V,3] and [N,J,3] float32 tensors expected")
-        coef, G = self._joints(verts, pose, betas, transl, jo)
+        coef, G = self._joints(verts if joints_from is None else joints_from, pose, betas, transl, jo)
         _lib.check(_lib.lib.cape_smpl_skin(_p(verts), 0 if verts.shape[0] == 1 else 3 * V, self._basis(coef.shape[1] - 9 * (J - 1)),
                                            coef.shape[1], _p(coef), _p(G), _p(d.ell_j), _p(d.ell_w), self.ell_width, _p(transl),
                                            J, V, N, _p(vo), 3 * V, _stream()), "cape_smpl_skin")
         return vo, jo
 
-    def forward(self, verts, pose, betas=None, transl=None, out=None):
+    def forward(self, verts, pose, betas=None, transl=None, out=None, joints_from=None):
         """Pose N meshes.  ``verts`` [N,V,3] or [1,V,3] (one rest body for every pose; None: the template), ``pose`` [N,J*3]
         axis-angle (joint 0 = global orientation), ``betas`` [N,<=B], ``transl`` [N,3]: float32 tensors on this model's device.
         Returns (vertices [N,V,3], joints [N,J,3]); with ``out`` = that pair preallocated, nothing synchronises the host, so
-        the call can be captured in a graph.  No gradient: see ``forward_diff``."""
-        return self._launch(*self._arguments(verts, pose, betas, transl, grad=False), out=out)
+        the call can be captured in a graph.  No gradient: see ``forward_diff``.  ``joints_from`` [N or 1, V, 3]: regress the
+        joints from that body (plus the shape term) instead of from ``verts``; None is the forward as it always was."""
+        verts, pose, betas, transl = self._arguments(verts, pose, betas, transl, grad=False)
+        if joints_from is not None:
+            joints_from = self._body_argument("joints_from", joints_from, pose.shape[0])
+        return self._launch(verts, pose, betas, transl, out=out, joints_from=joints_from)
 
-    def forward_diff(self, verts, pose, betas=None, transl=None):
+    def unpose_workspace(self, N):
+        """A workspace for ``unpose`` of N samples with ``joints_from=None`` (cape_smpl_unpose_workspace_bytes)."""
+        nbytes = _lib.lib.cape_smpl_unpose_workspace_bytes(self.J, N)
+        _lib.check(min(nbytes, 0), "cape_smpl_unpose_workspace_bytes")
+        return torch.empty((nbytes // 8,), dtype=torch.float64, device=self.device)
+
+    def unpose(self, posed, pose, betas=None, transl=None, joints_from=None, out=None, det_min=None, workspace=None):
+        """The inverse of ``forward``: ``posed`` [N,V,3] vertices in this model's topology and the ``pose`` / ``betas`` /
+        ``transl`` they were posed with (as in ``forward``) -> (rest [N,V,3], rest_joints [N,J,3]), the rest body with
+        ``forward(rest, pose, betas, transl) = posed`` and the joints ``forward`` regresses from it.
+        ``joints_from=None`` is the exact inverse: the joints depend on the unknown rest body, one 3J x 3J solve per sample
+        finds them (cape_smpl_unpose_joints, fp64).  ``joints_from`` [N or 1, V, 3] takes them from that body instead
+        (cape_smpl_joints), which inverts ``forward(..., joints_from=that body)``; against the plain forward it is off by
+        as far as the two bodies' joints differ (centimetres for a template body under clothing).
+        ``det_min`` [N] float32 (optional) receives min_v |det| of the blended skinning rotations: near zero the pose has
+        collapsed some vertex's transform and the rest body is ill-determined there.  With ``out`` = the returned pair and
+        ``workspace`` (``unpose_workspace(N)``) preallocated, nothing synchronises the host.  No gradient."""
+        posed, pose, betas, transl = self._arguments(posed, pose, betas, transl, grad=False)
+        J, V, d, N = self.J, self.V, self._dev, pose.shape[0]
+        if posed.shape[0] != N:
+            raise ValueError("posed: [%d, %d, 3] expected, got %s" % (N, V, tuple(posed.shape)))
+        if out is None:
+            out = (torch.empty((N, V, 3), dtype=torch.float32, device=d.device),
+                   torch.empty((N, J, 3), dtype=torch.float32, device=d.device))
+        to, jo = out
+        if tuple(to.shape) != (N, V, 3) or tuple(jo.shape) != (N, J, 3) or not (to.is_contiguous() and jo.is_contiguous()):
+            raise ValueError("out: contiguous [N,V,3] and [N,J,3] float32 tensors expected")
+        if det_min is not None and (det_min.dtype != torch.float32 or tuple(det_min.shape) != (N,) or det_min.device != d.device
+                                    or not det_min.is_contiguous()):
+            raise ValueError("det_min: a contiguous float32 [%d] tensor on %s expected" % (N, d.device))
+        B = 0 if betas is None else betas.shape[1]
+        if joints_from is None:
+            ws = self.unpose_workspace(N) if workspace is None else workspace
+            coef = torch.empty((N, B + 9 * (J - 1)), dtype=torch.float32, device=d.device)
+            G = torch.empty((N, J, 12), dtype=torch.float32, device=d.device)
+            _lib.check(_lib.lib.cape_smpl_unpose_joints(_p(posed), 3 * V, _p(d.rowptr), _p(d.colidx), _p(d.vals), _p(d.ell_j),
+                                                        _p(d.ell_w), self.ell_width, _p(pose), _p(betas), B, _p(d.jposedirs),
+                                                        _p(transl), self._parents_c, J, V, N, _p(ws),
+                                                        ws.numel() * ws.element_size(), _p(coef), _p(G), _p(jo), None,
+                                                        _p(det_min), _stream()), "cape_smpl_unpose_joints")
+        else:
+            joints_from = self._body_argument("joints_from", joints_from, N)
+            coef, G = self._joints(joints_from, pose, betas, transl, None)
+            self._joints(joints_from, torch.zeros_like(pose), betas, None, jo)       # zero pose: the posed joints are the rest joints
+            if det_min is not None:
+                det_min.fill_(float("inf"))
+        _lib.check(_lib.lib.cape_smpl_unpose_skin(_p(posed), 3 * V, self._basis(B), coef.shape[1], _p(coef), _p(G), _p(d.ell_j),
+                                                  _p(d.ell_w), self.ell_width, _p(transl), J, V, N, _p(to), 3 * V, _p(det_min),
+                                                  _stream()), "cape_smpl_unpose_skin")
+        return to, jo
+
+    def unpose_np(self, posed, pose, betas=None, transl=None, joints_from=None):
+        """``unpose``, numpy in, numpy out: (rest [N,V,3], rest_joints [N,J,3]) float32."""
+        t = lambda a: None if a is None else torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float32).to(self.device)
+        with torch.no_grad():
+            pose = np.asarray(pose).reshape(-1, 3 * self.J)
+            posed = np.asarray(posed).reshape(-1, self.V, 3)
+            jf = None if joints_from is None else np.asarray(joints_from).reshape(-1, self.V, 3)
+            to, jo = self.unpose(t(posed), t(pose), t(betas), t(transl), joints_from=t(jf))
+            return to.cpu().numpy(), jo.cpu().numpy()
+
+    def forward_diff(self, verts, pose, betas=None, transl=None, joints_from=None):
         """``forward`` (same arguments, same checks, bitwise the same values) as an autograd function: gradients on the returned
         vertices and / or joints flow to whichever of ``verts`` ([1,V,3]: summed over the samples), ``pose``, ``betas`` and
-        ``transl`` require them.  The inputs are all that is saved; backward recomputes the joint transforms."""
+        ``transl`` require them.  The inputs are all that is saved; backward recomputes the joint transforms.  The backward
+        kernels assume the joints come from ``verts``: ``joints_from`` is refused."""
+        if joints_from is not None:
+            raise NotImplementedError("cape_amd.smpl: forward_diff has no joints_from (use forward, which carries no gradient)")
         verts, pose, betas, transl = self._arguments(verts, pose, betas, transl, grad=True)
         return _PoseFn.apply(self, verts, pose, betas, transl)
 
@@ -333,8 +417,10 @@ class _DressArrays(object):
 
     def __init__(self, mean, std, clothing_idx, minimal_shape, V, device):
         dev = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
-        mask = np.zeros(V, np.float32)
-        mask[np.asarray(clothing_idx, dtype=np.int64)] = 1.0
+        self.every_vertex = clothing_idx is None
+        mask = np.ones(V, np.float32) if self.every_vertex else np.zeros(V, np.float32)
+        if not self.every_vertex:
+            mask[np.asarray(clothing_idx, dtype=np.int64)] = 1.0
         self.mean, self.std = dev(np.reshape(mean, (V, 3))), dev(np.reshape(std, (V, 3)))
         self.minimal, self.mask = dev(np.reshape(minimal_shape, (V, 3))), dev(mask)
         self.V = V
@@ -349,6 +435,19 @@ class _DressArrays(object):
                                             _p(out), 3 * V, N, V, _stream()), "cape_smpl_dress")
         return out
 
+    def undress(self, T, out=None):
+        """The right-inverse of the call: (mask * (T - minimal) - mean) / std (cape_smpl_undress)."""
+        N, V = T.shape[0], self.V
+        if T.dtype != torch.float32 or not T.is_contiguous() or tuple(T.shape[1:]) != (V, 3):
+            raise ValueError("T: contiguous float32 [N, %d, 3] expected" % V)
+        if out is None:
+            out = torch.empty((N, V, 3), dtype=torch.float32, device=T.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (N, V, 3) or not out.is_contiguous():
+            raise ValueError("out: contiguous float32 [%d, %d, 3] expected" % (N, V))
+        _lib.check(_lib.lib.cape_smpl_undress(_p(T), 3 * V, _p(self.mean), _p(self.std), None if self.every_vertex else _p(self.mask),
+                                              _p(self.minimal), _p(out), 3 * V, N, V, _stream()), "cape_smpl_undress")
+        return out
+
     def diff(self, disp):
         """The same with a gradient to ``disp``: mask * std * the incoming gradient (cape_smpl_dress_bwd)."""
         if disp.dtype != torch.float32 or not disp.is_contiguous() or tuple(disp.shape[1:]) != (self.V, 3):
@@ -360,6 +459,14 @@ def dress(disp, mean, std, clothing_idx, minimal_shape):
     """demos.py:155-161: ``minimal_shape + mask(clothing_idx) * (disp * std + mean)`` for a device tensor ``disp`` [N,V,3];
     the other arguments are host arrays.  Returns the clothed rest bodies [N,V,3] on the device."""
     return _DressArrays(mean, std, clothing_idx, minimal_shape, disp.shape[1], disp.device)(disp)
+
+
+def undress(T, mean, std, clothing_idx, minimal_shape):
+    """The way back from ``dress`` (reference lib/prep_data.py:74 packs ``v_cano - minimal`` for training):
+    ``(mask(clothing_idx) * (T - minimal_shape) - mean) / std`` for a device tensor ``T`` [N,V,3] of rest bodies; the other
+    arguments are host arrays, ``clothing_idx=None`` means every vertex.  ``dress(undress(T))`` is ``T`` on the clothing
+    vertices and ``minimal_shape`` elsewhere.  Returns the normalised displacements [N,V,3] on the device."""
+    return _DressArrays(mean, std, clothing_idx, minimal_shape, T.shape[1], T.device).undress(T)
 
 
 def dress_diff(disp, mean, std, clothing_idx, minimal_shape):

@@ -957,6 +957,52 @@ int cape_smpl_weighted_l2(const float *pred, int64_t pred_sample_stride, const f
                           int64_t grad_sample_stride, void *stream);
 
 /*
+ * SMPL posing, inverse (cape_amd/csrc/smpl/smpl_unpose.hip).  Given posed vertices `posed` [N][V][3] in SMPL topology and
+ * the pose (betas, transl) they were posed with, the rest body T with forward(T) = posed -- demos.py's posing step
+ * (:267-283, 312-326) run backwards -- and from there the normalised displacements the network takes.  The forward
+ * regresses its joints from the rest body it is given, so the rest joints Jn are part of the unknown.  With W_j the world
+ * rotation of joint j, D_m = W_parent(m) - W_m (D_0 = I - W_0), Mrot_v = sum_j W[v][j] W_j and acc_v = basis_v . coef:
+ *   G_j.t = sum over m on the path root .. j of D_m Jn_m          (the skinning translations are linear in Jn)
+ *   (I + Q L) Jn = c,   Q[a][j] = sum_v J_regressor[a][v] W[v][j] Mrot_v^-1,   L[j][m] = D_m for m on j's path, else 0,
+ *   c = J_regressor . (Mrot^-1 (posed - transl)) - jposedirs . pf  (the shape term enters both sides and cancels)
+ *   T_v = Mrot_v^-1 (posed_v - transl - sum_j W[v][j] G_j.t) - acc_v
+ * jposedirs [9(J-1)][J][3] = J_regressor . posedirs, built at load next to jshapedirs; the other arrays as above.
+ * cape_smpl_unpose_joints: one workgroup per sample.  Rodrigues in fp32 as cape_smpl_joints computes it (coef holds the same
+ * values in the same layout), the chain, the assembly of the 3J x 3J system over the regressor's nonzeros and Gaussian
+ * elimination with partial pivoting in fp64, in the caller's workspace (staged in LDS while 8 * 3J * (3J + 1) bytes fit 43 KB:
+ * J <= 24).  Every loop has a fixed trip count: a singular or non-finite system gives non-finite outputs.  Writes coef
+ * [N][B + 9(J-1)] and G [N][J][12] as cape_smpl_joints does, rest_joints [N][J][3] = Jn and joints [N][J][3] = A_j.t + transl
+ * (each NULL: not written), and sets det_min [N] (NULL: absent) to +inf for cape_smpl_unpose_skin.
+ * cape_smpl_unpose_skin: cape_smpl_skin's tiling (cape_smpl_skin_tile).  Per vertex and sample M = sum_j W[v][j] G_j in fp32
+ * in increasing joint order -- the forward's M bit for bit --, its 3x3 inverse by adjugate / determinant and the product in
+ * fp64, rounded once.  coef / G from cape_smpl_unpose_joints, or from cape_smpl_joints on a body of the caller's choice
+ * (explicit joints: cheaper, and the inverse of a forward that took its joints from that body).  det_min [N] (NULL: not
+ * wanted) must hold +inf (or a bound) on entry and takes min_v |det Mrot_v| by an integer atomic minimum on the bit pattern;
+ * a NaN determinant is not recorded.  Deterministic; no host synchronisation, no allocation.
+ * Errors: CAPE_EINVAL for NULL operands, N < 1, strides below 3V, J outside 1..64, a short or misaligned workspace, index
+ * products beyond 32 bits; CAPE_ERANGE for a tree that is not parent-ordered; all decided before any launch.
+ */
+/* bytes of cape_smpl_unpose_joints' workspace: 8 * N * 3J * (3J + 1); negative: the CAPE_E* code */
+int64_t cape_smpl_unpose_workspace_bytes(int32_t J, int32_t N);
+/* replaces the joint regression of demos.py:267-283 / 312-326 in the inverse direction (see above) */
+int cape_smpl_unpose_joints(const float *posed, int64_t posed_sample_stride, const int32_t *jreg_rowptr,
+                            const int32_t *jreg_colidx, const float *jreg_vals, const int32_t *ell_joint,
+                            const float *ell_weight, int32_t ell_width, const float *pose, const float *betas, int32_t B,
+                            const float *jposedirs, const float *transl, const int32_t *parents, int32_t J, int32_t V,
+                            int32_t N, void *workspace, int64_t workspace_bytes, float *coef, float *G, float *rest_joints,
+                            float *joints, float *det_min, void *stream);
+/* the inverse of cape_smpl_skin (smplx SMPL forward, demos.py:22, :267-283): out [N][V][3] = T */
+int cape_smpl_unpose_skin(const float *posed, int64_t posed_sample_stride, const float *basis, int32_t K, const float *coef,
+                          const float *G, const int32_t *ell_joint, const float *ell_weight, int32_t ell_width,
+                          const float *transl, int32_t J, int32_t V, int32_t N, float *out, int64_t out_sample_stride,
+                          float *det_min, void *stream);
+/* disp[n, v, :] = (mask[v] * (T[n, v, :] - minimal[v, :]) - mean[v, :]) / std[v, :] (mask NULL: ones): the reference's
+ * lib/prep_data.py:74 (v_cano - minimal) with the normalisation of its data loader, the right-inverse of cape_smpl_dress:
+ * dress(undress(T)) = minimal + mask * (T - minimal) */
+int cape_smpl_undress(const float *T, int64_t T_sample_stride, const float *mean, const float *std_, const float *mask,
+                      const float *minimal, float *disp, int64_t disp_sample_stride, int32_t N, int32_t V, void *stream);
+
+/*
  * Per-vertex Euclidean error and its statistics (cape_amd/csrc/eval/vertex_error.hip): the auto-encoding error of
  * demos.py:68-78, there numpy on predictions copied to the host.  pred / gt [N, V, 3] in normalised units (pred with leading
  * dimension ldp >= 3, pad never read; gt dense), std_ [V, 3] the training set's, idx [Vc] vertex indices in [0, V), in the

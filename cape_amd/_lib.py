@@ -218,6 +218,9 @@ SIGNATURES = {
                                           _p, _p, _p, _p, _p, _p]),
     "cape_smpl_unpose_skin": (C.c_int, [_p, _i64, _p, _i32, _p, _p, _p, _p, _i32, _p, _i32, _i32, _i32, _p, _i64, _p, _p]),
     "cape_smpl_undress": (C.c_int, [_p, _i64, _p, _p, _p, _p, _p, _i64, _i32, _i32, _p]),
+    "cape_vertex_normals_workspace_bytes": (_i64, [_i32, _i32]),
+    "cape_vertex_normals_fwd": (C.c_int, [_p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _p]),
+    "cape_vertex_normals_bwd": (C.c_int, [_p, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _p, _i64, _p]),
 }
 
 # bf16-storage variants with the argument list of their fp32 namesake (include/cape_hip.h, last section)

@@ -1681,24 +1681,32 @@ class CAPE(base_model):
                                          body.V, self.device)
         return body, pose, transl, dressing, cond, cond2
 
-    def decode_posed(self, data, cond, cond2, pose, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None):
+    def decode_posed(self, data, cond, cond2, pose, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None,
+                     return_normals=False):
         """``decode`` followed by demos.py's posing step (:155-161 / :207-213 dress, :267-283 / :312-326 SMPL forward), on
         the device per padded batch: decoder -> cape_smpl_dress -> cape_smpl_joints -> cape_smpl_skin.  ``pose`` [size, 72]
         or [1, 72] (one pose for every sample), ``transl`` likewise or None; ``body_model`` a ``cape_amd.smpl.SMPL`` (or the
         object ``cape_amd.smpl.create`` returns); ``minimal_shape`` defaults to the template mesh.  Batching, padding and the
-        one-condition-many-samples rule are decode's.  Returns (posed, clothed_unposed) [size, V, 3] float32."""
+        one-condition-many-samples rule are decode's.  Returns (posed, clothed_unposed) [size, V, 3] float32; with
+        ``return_normals`` a third array, the per-vertex normals of the posed meshes [size, V, 3] (``SMPL.vertex_normals`` on
+        the model's faces: uniform weights, unit length, zero where a vertex has no non-degenerate face), computed on the
+        device per batch before the copy to the host."""
         body, pose, transl, dressing, _, _ = self._posed_arguments(data.shape[0], body_model, pose, transl,
                                                                    (mean, std, clothing_idx, minimal_shape))
         self._open_pass()
-        posed, clothed = [], []
+        posed, clothed, normals = [], [], []
         with torch.no_grad():
             for begin, end, x in self._decoded(data, cond, cond2):
                 nb = end - begin
                 T = dressing(x[:nb].float().contiguous())
                 vo, _ = body.forward(T, self._padded(pose, begin, end)[:nb], None,
                                      None if transl is None else self._padded(transl, begin, end)[:nb])
+                if return_normals:
+                    normals.append(body.vertex_normals(vo).cpu().numpy())
                 posed.append(vo.cpu().numpy())
                 clothed.append(T.cpu().numpy())
+        if return_normals:
+            return np.concatenate(posed, 0), np.concatenate(clothed, 0), np.concatenate(normals, 0)
         return np.concatenate(posed, 0), np.concatenate(clothed, 0)
 
     def encode_posed(self, posed, pose, cond, cond2, body_model, mean, std, clothing_idx=None, minimal_shape=None, transl=None,
@@ -1745,7 +1753,8 @@ class CAPE(base_model):
         return res + (np.concatenate(disps, 0),) if return_disp else res
 
     def fit_posed(self, target, pose, cond, cond2, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None, z0=None,
-                  weights=None, steps=200, lr=0.1, lambda_z=0.0, lambda_edge=0.0, optimize_pose=False, optimize_transl=False):
+                  weights=None, steps=200, lr=0.1, lambda_z=0.0, lambda_edge=0.0, optimize_pose=False, optimize_transl=False,
+                  lambda_vnormal=0.0):
         """The latent codes that explain posed meshes: gradient descent (Adam) on ``z`` through
         decoder -> cape_smpl_dress -> SMPL posing, all on the device (``smpl.dress_diff`` / ``SMPL.forward_diff``).
 
@@ -1755,9 +1764,14 @@ class CAPE(base_model):
         per-vertex weights of the data term (ones).  Per sample the objective is
 
             sum_v w_v |posed_v - target_v|^2 / sum_v w_v  +  lambda_z mean(z^2)  [+ lambda_edge edge(posed, target)]
+                [+ lambda_vnormal sum_v w_v (1 - n_v(posed) . n_v(target)) / sum_v w_v]
 
         (edge: the training loss's edge term between the posed mesh and the target, per sample; asking for it costs one
-        element-wise product and one sum on [N, V, 3] per step in torch, where the two gradients meet).  The leaves are ``z``, and
+        element-wise product and one sum on [N, V, 3] per step in torch, where the two gradients meet.  vnormal: VERTEX normals
+        on the body model's faces, ``SMPL.vertex_normals_diff`` -- not the training option ``lambda_normal``, which is face
+        normals; the target's normals are computed once per batch, the term's gradient -lambda_vnormal w_v n_v(target) / sum w
+        is a constant of the batch and enters the one backward call next to the data gradient; the term's value costs one
+        product and one sum on [N, V, 3] per step in torch.)  The leaves are ``z``, and
         ``pose`` / ``transl`` with ``optimize_pose`` / ``optimize_transl`` (``transl`` then starts at zero when None); the
         samples are independent.  The model's variables take no gradient and no weight-gradient kernel runs; optimiser state
         and gradient buckets stay as a ``decode`` call leaves them.  The defaults (200 steps, lr 0.1, lambda_z 0) come from
@@ -1768,7 +1782,8 @@ class CAPE(base_model):
 
         Returns a dict: ``z`` [size, nz], ``pose`` [size, 3J], ``transl`` [size, 3] or None, ``posed`` / ``clothed``
         [size, V, 3] for the returned leaves, ``loss`` [steps + 1, size] the data term per sample (row 0: before the first
-        update)."""
+        update), and with ``lambda_vnormal > 0`` ``normal`` [steps + 1, size], the vertex-normal term per sample before the
+        multiplication by ``lambda_vnormal``."""
         from . import smpl as smpl_mod
         body = getattr(body_model, 'model', body_model)
         target = np.asarray(target, dtype=np.float32)
@@ -1786,13 +1801,16 @@ class CAPE(base_model):
         if w.shape != (V,) or not float(w.sum()) > 0.0:
             raise ValueError("weights: [%d] with a positive sum expected" % V)
         steps = int(steps)
+        lambda_vnormal = float(lambda_vnormal)
+        if not np.isfinite(lambda_vnormal) or lambda_vnormal < 0:
+            raise ValueError("lambda_vnormal must be finite and >= 0, got %r" % (lambda_vnormal,))
         inv_wsum = 1.0 / float(w.astype(np.float64).sum())
         w_dev = self._dev(w)
         self._open_pass()
         if lambda_edge:
             _, ed, vptr, vidx = self._edge_tables()
             no_ref = torch.zeros((V, 3), dtype=torch.float32, device=self.device)
-        res = dict(z=[], pose=[], transl=[], posed=[], clothed=[], loss=[])
+        res = dict(z=[], pose=[], transl=[], posed=[], clothed=[], loss=[], normal=[])
         # the model's variables are constants here: no gradient bucket to write into and, while the steps run, nothing that
         # requires a gradient (the ops then skip their weight-gradient kernels)
         grad_views, self._grad_views = self._grad_views, {}
@@ -1814,6 +1832,14 @@ class CAPE(base_model):
                 opt = torch.optim.Adam(leaves, lr=float(lr))
                 loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
                 grad = torch.zeros((bs, V, 3), dtype=torch.float32, device=self.device)       # padded rows stay zero
+                if lambda_vnormal:
+                    # w_v n_v(target) / sum w in fp64 (the term's value is summed in fp64), padded rows zero; the term's
+                    # gradient to the posed normals is -lambda_vnormal times that, the same at every step
+                    with torch.no_grad():
+                        tnw = body.vertex_normals(tgt).double() * (w_dev.double() * inv_wsum)[None, :, None]
+                        tnw[nb:] = 0.0
+                        g_normal = (-lambda_vnormal * tnw).float()
+                    normal = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
 
                 def evaluate(step, want_grad):
                     with self.variable_scope('generator'):
@@ -1821,35 +1847,49 @@ class CAPE(base_model):
                     T = dressing.diff(x.float().contiguous())
                     posed, _ = body.forward_diff(T, bp, None, bt)
                     smpl_mod.weighted_l2(posed, tgt, w_dev, inv_wsum, nb, loss[step], grad if want_grad else None)
-                    return T, posed
+                    nrm = None
+                    if lambda_vnormal:
+                        nrm = body.vertex_normals_diff(posed) if want_grad else body.vertex_normals(posed)
+                        # sum_v w_v / sum w = 1: the term is 1 - sum_v w_v n_v . n_v(target) / sum w
+                        normal[step, :nb] = (1.0 - (nrm.detach().double() * tnw).sum((1, 2)))[:nb].float()
+                    return T, posed, nrm
 
                 freeze(True)
                 try:
                     for step in range(steps):
-                        T, posed = evaluate(step, True)
+                        T, posed, nrm = evaluate(step, True)
                         opt.zero_grad(set_to_none=True)
+                        roots, seeds = [posed], [grad]
                         if lambda_edge:
                             # the batch mean of the training loss's edge term, scaled back to a sum over the samples
                             e_total, _ = ops.ReconEdgeLossFn.apply(posed[:nb], tgt[:nb], no_ref, ed, vptr, vidx, 0.0,
                                                                    float(lambda_edge) * nb)
-                            torch.autograd.backward([posed, e_total], [grad, None])
-                        else:
-                            torch.autograd.backward([posed], [grad])
+                            roots.append(e_total)
+                            seeds.append(None)
+                        if lambda_vnormal:
+                            roots.append(nrm)
+                            seeds.append(g_normal)
+                        torch.autograd.backward(roots, seeds)
                         if lambda_z:
                             z.grad.add_(z.detach(), alpha=2.0 * float(lambda_z) / nz)
                         opt.step()
                 finally:
                     freeze(False)
                 with torch.no_grad():            # the returned leaves as decode_posed evaluates them, kernel for kernel
-                    T, posed = evaluate(steps, False)
+                    T, posed, _ = evaluate(steps, False)
                 res['z'].append(z.detach()[:nb].cpu().numpy())
                 res['pose'].append(bp.detach()[:nb].cpu().numpy())
                 res['transl'].append(None if bt is None else bt.detach()[:nb].cpu().numpy())
                 res['posed'].append(posed[:nb].cpu().numpy())
                 res['clothed'].append(T[:nb].cpu().numpy())
                 res['loss'].append(loss[:, :nb].cpu().numpy())
+                if lambda_vnormal:
+                    res['normal'].append(normal[:, :nb].cpu().numpy())
         finally:
             self._grad_views = grad_views
         cat = lambda k, ax=0: np.concatenate(res[k], ax)
-        return dict(z=cat('z'), pose=cat('pose'), transl=None if transl is None else cat('transl'), posed=cat('posed'),
-                    clothed=cat('clothed'), loss=cat('loss', 1))
+        out = dict(z=cat('z'), pose=cat('pose'), transl=None if transl is None else cat('transl'), posed=cat('posed'),
+                   clothed=cat('clothed'), loss=cat('loss', 1))
+        if lambda_vnormal:
+            out['normal'] = cat('normal', 1)
+        return out

@@ -8,6 +8,8 @@ bodies (reference demos.py:155-161, 207-213 and :249-331, which go through ``smp
   SMPL.pose(...)             the same on numpy arrays
   SMPL.unpose(...)           the inverse of ``forward``: posed vertices + pose -> the rest body and its joints
                              (cape_smpl_unpose_joints / cape_smpl_unpose_skin); ``unpose_np`` on numpy arrays
+  SMPL.vertex_normals(...)   per-vertex normals of meshes in the model's topology (``cape_amd.vertex_normals`` on the model's
+                             ``faces``); ``vertex_normals_diff`` with a gradient, ``vertex_normals_np`` on numpy arrays
   dress(...)                 de-normalise + clothing mask + minimal body (cape_smpl_dress)
   undress(...)               its right-inverse: rest body -> normalised displacements (cape_smpl_undress)
   dress_diff(...)            the same with a gradient to the displacements (cape_smpl_dress_bwd)
@@ -145,6 +147,7 @@ class SMPL(object):
                             jshapedirs=(jsd, np.float32), jposedirs=(jpd, np.float32), v_template=(m["v_template"], np.float32),
                             jt_colptr=(tp, np.int32), jt_rowidx=(ti, np.int32), jt_vals=(jt.data, np.float32))
         self._dev = None
+        self._normals = None
         self._parents_c = (C.c_int32 * J)(*[int(x) for x in self.parents])
 
     @property
@@ -359,6 +362,27 @@ class SMPL(object):
         return dT, dpose, dbetas, dtransl
 
     __call__ = forward
+
+    def _vertex_normals(self):
+        """``VertexNormals`` on the model's own ``faces``, validated and uploaded on first use (a model whose faces are not a
+        valid triangle list still poses)."""
+        if self._normals is None:
+            from .vertex_normals import VertexNormals
+            self._normals = VertexNormals(self.faces, self.V, device=self._device)
+        return self._normals
+
+    def vertex_normals(self, verts, out=None):
+        """Per-vertex normals [N, V, 3] of device meshes ``verts`` [N, V, 3] in the model's topology -- posed or not -- as
+        ``cape_amd.vertex_normals.VertexNormals.forward`` computes them (uniform weights; no gradient)."""
+        return self._vertex_normals().forward(verts, out)
+
+    def vertex_normals_diff(self, verts):
+        """``vertex_normals`` as an autograd function: gradients on the normals flow to ``verts``."""
+        return self._vertex_normals().diff(verts)
+
+    def vertex_normals_np(self, verts):
+        """``vertex_normals``, numpy in, numpy out."""
+        return self._vertex_normals().np(verts)
 
     def pose(self, verts, pose, betas=None, transl=None):
         """numpy in, numpy out: (vertices [N,V,3], joints [N,J,3]) float32."""

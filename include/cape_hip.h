@@ -60,6 +60,9 @@
  *   cape_vertex_error / cape_error_stats
  *                       demos.py:68-78 the auto-encoding error: de-normalised per-vertex Euclidean distance on the clothing
  *                       vertices and its mean / std / median (np.mean, np.std, np.median over all samples and vertices).
+ *   cape_vertex_normals_fwd / cape_vertex_normals_bwd
+ *                       lib/losses.py:54-80 estimate_vertex_normals on lib/utils.py:119-135 TriNormals / NormalizedNx3 (never
+ *                       called by the reference) for a batch of meshes, and its gradient w.r.t. the vertices.
  */
 #ifndef CAPE_HIP_H
 #define CAPE_HIP_H
@@ -1030,6 +1033,37 @@ int64_t cape_error_stats_workspace_bytes(int32_t S, int32_t Vc, int32_t R);
 int cape_error_stats(const float *dist, int32_t S, int32_t Vc, const int64_t *ranks, int32_t R, double *out_moments,
                      float *out_order, double *per_vertex, double *per_sample, void *workspace, int64_t workspace_bytes,
                      void *stream);
+
+/*
+ * Per-vertex normals (cape_amd/csrc/mesh/vertex_normals.hip): the reference's estimate_vertex_normals (lib/losses.py:54-80,
+ * its TensorFlow restatement of psbody.mesh's routine on lib/utils.py:119-135 TriNormals / NormalizedNx3; one mesh per call
+ * there, and nothing calls it).  x [N, V, 3] with leading dimension ldx >= 3 (pad never read), samples V rows apart; faces
+ * [F, 3] int32 vertex indices in [0, V), no vertex twice in a face; vert_face_ptr [V + 1] / vert_face_idx [3 F] per vertex its
+ * incident corners 3 * face + corner in a fixed order (cape_amd.graph.vertex_face_table):
+ *   m_f = (x[i1] - x[i0]) x (x[i2] - x[i0]);  u_f = m_f / sqrt(m_f.m_f + [m_f.m_f == 0])
+ *   s_v = sum of u_f over the faces that use v, in list order (uniform weights; the area-weighted variant sums m_f instead)
+ *   normals[n, v] = s_v / sqrt(s_v.s_v + [s_v.s_v == 0])
+ * A degenerate face adds 0; a vertex without faces, or whose unit normals cancel, gets 0.  normals [N, V, 3] with leading
+ * dimension ldn >= 3 (pad never written).  One launch, one work item per (sample, vertex), which recomputes the unit normal of
+ * each incident face from its corners; fp32 in and out, fp64 in between.
+ *
+ * cape_vertex_normals_bwd: dx [N, V, 3] (leading dimension ldd >= 3, pad never written; overwritten, not accumulated) =
+ * d L / d x for gnormals = d L / d normals (leading dimension ldg >= 3), the gradient of the expression as written with both
+ * zero guards constant:
+ *   h_v = (g_v - n_v (n_v.g_v)) / |s_v|';  G_f = h_i0 + h_i1 + h_i2;  gamma_f = (G_f - u_f (u_f.G_f)) / |m_f|'
+ *   dx[corner k of f] += gamma_f x (x[k+2] - x[k+1])      (corners cyclic; ' = the guarded root)
+ * Two launches: h into the workspace (cape_vertex_normals_workspace_bytes(N, V) = 12 N V bytes, no initialisation), then per
+ * vertex the sum over its incident corners in list order.  No atomics: the same inputs give the same bits.
+ * Errors: CAPE_EINVAL for NULL operands, N, V, F < 1, a leading dimension below 3, a short workspace, N V or 3 F >= 2^31 (work
+ * items and table entries are int32); all decided before any launch.  The tables' contents are the caller's to validate.
+ */
+int64_t cape_vertex_normals_workspace_bytes(int32_t N, int32_t V);
+int cape_vertex_normals_fwd(const float *x, int32_t ldx, const int32_t *faces, const int32_t *vert_face_ptr,
+                            const int32_t *vert_face_idx, int32_t N, int32_t V, int32_t F, float *normals, int32_t ldn,
+                            void *stream);
+int cape_vertex_normals_bwd(const float *x, int32_t ldx, const float *gnormals, int32_t ldg, const int32_t *faces,
+                            const int32_t *vert_face_ptr, const int32_t *vert_face_idx, int32_t N, int32_t V, int32_t F, float *dx,
+                            int32_t ldd, void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

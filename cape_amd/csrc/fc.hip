@@ -113,9 +113,8 @@ __global__ __launch_bounds__(256) void fc_long_bwd_kernel(LongArgs A, const floa
     const int lo = threadIdx.x & 63, hi = threadIdx.x >> 6;
     // weight gradient rows (coalesced over j)
     for (int m = 0; m < A.nmat; ++m) {
-        if (!A.dW[m]) continue;
         const float *g = gs + m * N * out;
-        for (int j0 = 0; j0 < out; j0 += 64) {
+        for (int j0 = 0; A.dW[m] && j0 < out; j0 += 64) {
             const int j = j0 + lo;
             if (j >= out) continue;
             for (int il = hi; il < rows; il += 4) {
@@ -124,7 +123,7 @@ __global__ __launch_bounds__(256) void fc_long_bwd_kernel(LongArgs A, const floa
                 A.dW[m][(long long)(i0 + il) * out + j] = s;
             }
         }
-        if (blockIdx.x == 0 && A.db[m]) {
+        if (blockIdx.x == 0 && A.db[m]) {                   // (also without a dW[m])
             for (int j = threadIdx.x; j < out; j += 256) {
                 float s = 0.f;
                 for (int n = 0; n < N; ++n) s += g[n * out + j];
@@ -620,7 +619,8 @@ extern "C" int cape_fc_long_bwd(const float *x, int32_t ldx, int32_t N, int32_t 
         if (!A.g[m]) return CAPE_EINVAL;
     bool v4 = N <= 16 && (out & 3) == 0 && (size_t)(16 * 64 + nmat * 16 * out) * 4 <= 60 * 1024;
     for (int m = 0; m < nmat; ++m) v4 = v4 && fc_al16(A.W[m]) && (!A.dW[m] || fc_al16(A.dW[m]));
-    bool m16 = fc_m16_on && v4 && (out == 64 || (out == 128 && nmat == 1)) && (!dx || ((lddx & 3) == 0 && fc_al16(dx)));
+    // the MFMA kernel stores dx in quads of columns: with in % 4 != 0 the last one would reach past in
+    bool m16 = fc_m16_on && v4 && (out == 64 || (out == 128 && nmat == 1)) && (!dx || ((in & 3) == 0 && (lddx & 3) == 0 && fc_al16(dx)));
     for (int m = 0; m < nmat; ++m) m16 = m16 && fc_al16(A.g[m]);
     if (m16) {
         const dim3 grid((in + FC_RS - 1) / FC_RS);
@@ -676,7 +676,16 @@ extern "C" int cape_fc_wide_bwd(const float *x, int32_t ldx, const float *g, int
                                 float *dx, int32_t lddx, void *workspace, int64_t workspace_bytes, void *stream) {
     if (!x || !g || !W || N < 1 || N > FC_MAXN || in < 1 || out < 1 || ldx < in || ldg < out) return CAPE_EINVAL;
     if (act < CAPE_ACT_NONE || act > CAPE_ACT_TANH || (act != CAPE_ACT_NONE && (!y || ldy < out))) return CAPE_EINVAL;
-    if ((long long)N * in * 4 > 48 * 1024 || ((long long)in * 65 + (long long)N * 64) * 4 > 60 * 1024) return CAPE_EINVAL;
+    if ((long long)N * in * 4 > 48 * 1024) return CAPE_EINVAL;
+    // the data gradient's kernel is chosen before anything is launched: only the generic one holds [in][65] + [N][64] in LDS
+    const bool dx_m16 = dx && fc_m16_on && N <= 16 && (out & 63) == 0 && (in == 64 || in == 128 || in == 256) && fc_al16(W) && fc_al16(g) &&
+                        (ldg & 3) == 0 && (act == CAPE_ACT_NONE || ((ldy & 3) == 0 && fc_al16(y)));
+    const bool dx_v4 = dx && !dx_m16 && N <= 16 && (in & 3) == 0 && fc_al16(workspace) && ((size_t)64 * (in + 4) + 16 * 64) * 4 <= 60 * 1024;
+    if (dx) {
+        if (lddx < in || !workspace) return CAPE_EINVAL;
+        if (!dx_m16 && !dx_v4 && ((long long)in * 65 + (long long)N * 64) * 4 > 60 * 1024) return CAPE_EINVAL;
+        if (workspace_bytes < cape_fc_wide_bwd_workspace_bytes(N, in, out)) return CAPE_EWORKSPACE;
+    }
     hipStream_t st = (hipStream_t)stream;
     if (dW || db) {
         const bool v4 = N <= 16 && (out & 3) == 0 && (ldg & 3) == 0 && fc_al16(g) && (!dW || fc_al16(dW)) && (!db || fc_al16(db)) &&
@@ -697,17 +706,13 @@ extern "C" int cape_fc_wide_bwd(const float *x, int32_t ldx, const float *g, int
         CAPE_LAUNCH_CHECK();
     }
     if (dx) {
-        if (lddx < in || !workspace) return CAPE_EINVAL;
-        if (workspace_bytes < cape_fc_wide_bwd_workspace_bytes(N, in, out)) return CAPE_EWORKSPACE;
         int chunks = (out + 63) / 64;
-        const bool m16 = fc_m16_on && N <= 16 && (out & 63) == 0 && (in == 64 || in == 128 || in == 256) && fc_al16(W) && fc_al16(g) && (ldg & 3) == 0 &&
-                         (act == CAPE_ACT_NONE || ((ldy & 3) == 0 && fc_al16(y)));
-        if (m16) {
+        if (dx_m16) {
             chunks = (chunks + FC_DXC - 1) / FC_DXC;             // partial slabs: one per FC_DXC chunks of 64 columns
             if (in == 64) CAPE_LAUNCH((fc_wide_bwd_dx_m16_kernel<1>), dim3(chunks), dim3(256), 0, st, g, ldg, y, ldy, act, N, out, W, (float *)workspace);
             else if (in == 128) CAPE_LAUNCH((fc_wide_bwd_dx_m16_kernel<2>), dim3(chunks), dim3(256), 0, st, g, ldg, y, ldy, act, N, out, W, (float *)workspace);
             else CAPE_LAUNCH((fc_wide_bwd_dx_m16_kernel<4>), dim3(chunks), dim3(256), 0, st, g, ldg, y, ldy, act, N, out, W, (float *)workspace);
-        } else if (N <= 16 && (in & 3) == 0 && fc_al16(workspace) && ((size_t)64 * (in + 4) + 16 * 64) * 4 <= 60 * 1024)
+        } else if (dx_v4)
             CAPE_LAUNCH(fc_wide_bwd_dx_partial_v4_kernel, dim3(chunks), dim3(256), ((size_t)64 * (in + 4) + 16 * 64) * 4, st, g, ldg, y, ldy, act, N, in,
                         out, W, (float *)workspace);
         else

@@ -2516,8 +2516,21 @@ class FcWideFn(torch.autograd.Function):
 _FC_LONG = 8192       # a side at least this long takes the weight-streaming kernels
 
 
+_FC_LDS = 60 * 1024 // 4       # floats of LDS the generic backward kernels of csrc/fc.hip may ask for
+
+
 def _fc_long_ok(x, kernels):
-    return x.is_cuda and x.dim() == 2 and x.shape[0] <= 64 and x.shape[1] >= _FC_LONG and x.shape[0] * kernels[0].shape[1] * len(kernels) <= 8192
+    """cape_fc_long_bwd serves the call whatever the alignment of the gradient views: xs [N][64] + g [nmat][N][out] + a
+    [64][65] weight tile of its generic kernel fit in LDS."""
+    N, out, nmat = x.shape[0], kernels[0].shape[1], len(kernels)
+    return x.is_cuda and x.dim() == 2 and N <= 64 and x.shape[1] >= _FC_LONG and N * out * nmat <= 8192 and \
+        N * 64 + nmat * N * out + 64 * 65 <= _FC_LDS
+
+
+def _fc_wide_ok(x, kin, kout):
+    """the same for cape_fc_wide_bwd: W [in][65] + dz [N][64] of its generic data-gradient kernel."""
+    N = x.shape[0]
+    return x.is_cuda and x.dim() == 2 and N <= 64 and kout >= _FC_LONG and kin <= 200 and N * kin <= 12288 and kin * 65 + N * 64 <= _FC_LDS
 
 
 def dense(x, kernel, bias, activation=None, grad_bufs=(None, None)):
@@ -2526,7 +2539,7 @@ def dense(x, kernel, bias, activation=None, grad_bufs=(None, None)):
     act = "none" if activation is None else "leaky"
     if _fc_long_ok(x, [kernel]):
         y = FcLongFn.apply(x, [grad_bufs], kernel, bias)[0]
-    elif x.is_cuda and x.dim() == 2 and x.shape[0] <= 64 and kout >= _FC_LONG and kin <= 200 and x.shape[0] * kin <= 12288:
+    elif _fc_wide_ok(x, kin, kout):
         return FcWideFn.apply(x, kernel, bias, act, grad_bufs[0], grad_bufs[1])
     else:
         y = torch.addmm(bias, x, kernel)

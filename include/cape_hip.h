@@ -743,8 +743,10 @@ int cape_vae_sample_kl_bwd(const float *mean, const float *logvar, const float *
  * long input (in >> out; nmat = 1 or 2 matrices sharing x, e.g. fc_mean / fc_var):
  *   fwd:  y_m[n,j] = b_m[j] + sum_i x[n,i] W_m[i,j]                 (two deterministic launches)
  *   bwd:  dW_m[i,j] = sum_n x[n,i] g_m[n,j];  db_m[j] = sum_n g_m[n,j];  dx[n,i] = sum_m sum_j g_m[n,j] W_m[i,j]
- *         (g_m contiguous [N,out]; dW / db arrays or entries may be NULL; dx may be NULL)
- * wide output (out >> in, N*in <= 12288, in <= 200):
+ *         (g_m contiguous [N,out]; dW / db arrays or entries may be NULL; dx may be NULL; N > 16 or out % 4 != 0 or
+ *         a W / dW off a 16-byte boundary needs N*64 + nmat*N*out + 64*65 <= 15360 floats of LDS, else CAPE_EINVAL)
+ * wide output (out >> in, N*in <= 12288; a dx outside the aligned N <= 16 forms needs in*65 + N*64 <= 15360 floats of
+ * LDS, else CAPE_EINVAL before anything is launched):
  *   fwd:  y[n,j] = act(b[j] + sum_i x[n,i] W[i,j])
  *   bwd:  dz = g * act'(y) (y = activation output);  dW[i,j] = sum_n x[n,i] dz[n,j];  db[j] = sum_n dz[n,j];
  *         dx[n,i] = sum_j dz[n,j] W[i,j]   (two-stage, workspace >= cape_fc_wide_bwd_workspace_bytes)

@@ -53,6 +53,16 @@ def test_dense_layers_on_the_register_tiled_kernels():
     assert r.returncode == 0 and " passed" in tail and "failed" not in tail, tail
 
 
+def test_dense_kernel_cases_on_the_register_tiled_kernels():
+    """CAPE_FC_MFMA=0: the kernel-level cases of tests/test_gpu_fc.py again; tests/fc_cases.py reads the knob as the library does,
+    so the table then asserts the register-tiled kernels on the MFMA shapes."""
+    env = dict(os.environ, CAPE_FC_MFMA="0")
+    r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(ROOT, "tests", "test_gpu_fc.py"), "-x", "-q", "-m", "gpu"],
+                       env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900)
+    tail = r.stdout.decode()[-1500:]
+    assert r.returncode == 0 and " passed" in tail and "failed" not in tail, tail
+
+
 def test_step_without_the_fused_activation_gradient():
     """CAPE_FUSE_ACT_GRAD=0 (op-by-op backward-prep in the encoder), alone and on round 3's arithmetic (CAPE_H2=0: the pure
     six-product reference leg), has to reproduce the reference golden at batch 16 and the twin's gradients."""

@@ -7,9 +7,9 @@
 // block = (sample, row chunk) -- instead of one block per (sample, group) walking a [V, C/G] slab of 12..68-byte row
 // segments (the first version: 0.8 TB/s, every cache line fetched by up to five different blocks).
 //   forward : partial sums per (sample, chunk, channel) of d = x - p_c and d^2 with the pivot p_c = x[n, 0, c]
-//             (single pass; the shift keeps sum(d^2) - sum(d)^2/n free of cancellation) -> per (sample, group) mean /
-//             rstd in float64 -> per (sample, channel) scale a = rstd*gamma and shift b = beta - mean*a ->
-//             y = relu(fma(a, x, b)).
+//             (single pass in float64 from the difference on, so that sum(d^2) - sum(d)^2/n holds however far the pivot
+//             row lies from the mean -- see gn_stat_partial_kernel) -> per (sample, group) mean / rstd in float64 -> per (sample, channel) scale
+//             a = rstd*gamma and shift b = beta - mean*a -> y = relu(fma(a, x, b)).
 //   backward: the ReLU mask is re-derived as fma(a, x, b) > 0 (bit-identical to the forward decision: same operands, same
 //             fma), so y is not read; partial sums of d' and d'*xhat per (sample, chunk, channel) -> per (sample, group)
 //             sums -> dx = A_c d' - (B_g + xhat C_g).
@@ -22,6 +22,8 @@
 // (ld % 4 == 0, so ld >= Cp = round_up(C, 4)); every pass works on Cp / 4 quads, the last quad loads its pad lanes (inside
 // the row, values unused) and stores / accumulates only the lanes below C.  The per-channel tables (partials, coef, bcoef)
 // use the stride Cp so that their float4 accesses stay aligned.
+// Row bounds (rowmax_out) are defined for rows of finite values: the lane-group form and cape_rowmax drop a NaN (fmaxf), the
+// rows-per-block form keeps it (maximum of the bit patterns).
 #include "common.h"
 
 namespace {
@@ -50,10 +52,62 @@ inline int grid_for(long long total) {
     return (int)(b < 1 ? 1 : b);
 }
 
-// coef layout per sample: [4][C] = a (rstd*gamma), b (beta - mean*a), r (rstd of the channel's group), mr (mean*rstd)
-// MODE 0 (forward statistics): terms S = sum(x - p), Q = sum((x - p)^2)
-// MODE 1 (backward):           terms s1 = sum(d'), s2 = sum(d' * xhat)
-template <int MODE>
+// coef layout per sample: [4][Cp] = a (rstd*gamma), b (beta - mean*a), r (rstd of the channel's group), mr (mean*rstd)
+//
+// Forward statistics: per (sample, chunk, channel) S = sum(x - p), Q = sum((x - p)^2) with the pivot p_c = x[n, 0, c], in
+// float64 from the difference to the workspace (the difference of two float32 is exact there; the pivot only keeps the sums
+// small).  With float32 differences, accumulators and partials a pivot k sigma off the group's mean cost (1 + k^2) roundings
+// of the variance per add: measured on an MI355X against 4 x the error of a two-pass float32 evaluation, rstd of unit-normal
+// data missed that bar by 4.2 x at 128-row chunks with one channel per group (a 4-sigma first row somewhere among 32768
+// groups), and a first row at 16 sigma by 15 x (1.1e-5 relative); in float64 the same cases stay under a third of it for
+// first rows up to 256 sigma at every chunk form (tests/gn_cases.py has the table).
+// thread = (channel quad, row lane): lane rl adds rows rl, rl + lanes, .. of the chunk, then lane 0 adds the lanes in index
+// order (deterministic).
+__global__ __launch_bounds__(256) void gn_stat_partial_kernel(const float *x, long long xs, int ldx, int V, int C, int RB,
+                                                              int chunks, double *part) {
+    __shared__ double red[256 * 4];
+    const int n = blockIdx.x / chunks, ch = blockIdx.x % chunks;
+    const int ra = ch * RB, rb = min(V, ra + RB);
+    const float *xb = x + (long long)n * xs;
+    const int Cp = (C + 3) & ~3;
+    double *pp = part + ((long long)n * chunks + ch) * 2 * Cp;
+    for (int cbase = 0; cbase < Cp; cbase += 256) {
+        const int cw = min(256, Cp - cbase);
+        const int c4n = cw >> 2;
+        const int lanes = 256 / c4n;
+        const int q = threadIdx.x % c4n, rl = threadIdx.x / c4n;
+        const int c = cbase + 4 * q;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0, q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+        if (rl < lanes) {
+            const float4 p = *reinterpret_cast<const float4 *>(xb + c);           // pivot: row 0 of this sample
+            const double p0 = (double)p.x, p1 = (double)p.y, p2 = (double)p.z, p3 = (double)p.w;
+            for (int r = ra + rl; r < rb; r += lanes) {
+                const float4 v = *reinterpret_cast<const float4 *>(xb + (long long)r * ldx + c);
+                const double d0 = (double)v.x - p0, d1 = (double)v.y - p1, d2 = (double)v.z - p2, d3 = (double)v.w - p3;
+                s0 += d0; s1 += d1; s2 += d2; s3 += d3;
+                q0 = fma(d0, d0, q0); q1 = fma(d1, d1, q1); q2 = fma(d2, d2, q2); q3 = fma(d3, d3, q3);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            double t0 = j ? q0 : s0, t1 = j ? q1 : s1, t2 = j ? q2 : s2, t3 = j ? q3 : s3;
+            __syncthreads();
+            red[4 * threadIdx.x] = t0; red[4 * threadIdx.x + 1] = t1; red[4 * threadIdx.x + 2] = t2; red[4 * threadIdx.x + 3] = t3;
+            __syncthreads();
+            if (rl == 0) {
+                for (int l = 1; l < lanes; ++l) {                       // fixed order: deterministic
+                    const double *v = red + 4 * (l * c4n + q);
+                    t0 += v[0]; t1 += v[1]; t2 += v[2]; t3 += v[3];
+                }
+                double *o = pp + (long long)j * Cp + c;                 // (pad lanes of the last quad: never read)
+                o[0] = t0; o[1] = t1; o[2] = t2; o[3] = t3;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// Backward: partial sums s1 = sum(d'), s2 = sum(d' * xhat) per (sample, chunk, channel), float32, the same lane split.
 __global__ __launch_bounds__(256) void gn_partial_kernel(const float *x, long long xs, int ldx, const float *dy, long long dys,
                                                          int lddy, const float *coef, int relu, int V, int C, int RB,
                                                          int chunks, float *part) {
@@ -71,30 +125,20 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float *x, long lo
         const int c = cbase + 4 * q;
         float4 t0 = make_float4(0.f, 0.f, 0.f, 0.f), t1 = t0;
         if (rl < lanes) {
-            if (MODE == 0) {
-                const float4 p = *reinterpret_cast<const float4 *>(xb + c);           // pivot: row 0 of this sample
-                for (int r = ra + rl; r < rb; r += lanes) {
-                    const float4 v = *reinterpret_cast<const float4 *>(xb + (long long)r * ldx + c);
-                    const float dx_ = v.x - p.x, dy_ = v.y - p.y, dz_ = v.z - p.z, dw_ = v.w - p.w;
-                    t0.x += dx_; t0.y += dy_; t0.z += dz_; t0.w += dw_;
-                    t1.x = fmaf(dx_, dx_, t1.x); t1.y = fmaf(dy_, dy_, t1.y); t1.z = fmaf(dz_, dz_, t1.z); t1.w = fmaf(dw_, dw_, t1.w);
+            const float *cf = coef + (long long)n * 4 * Cp + c;
+            const float4 a = *reinterpret_cast<const float4 *>(cf), b = *reinterpret_cast<const float4 *>(cf + Cp);
+            const float4 rr = *reinterpret_cast<const float4 *>(cf + 2 * Cp), mr = *reinterpret_cast<const float4 *>(cf + 3 * Cp);
+            const float *gb = dy + (long long)n * dys;
+            for (int r = ra + rl; r < rb; r += lanes) {
+                const float4 v = *reinterpret_cast<const float4 *>(xb + (long long)r * ldx + c);
+                float4 d = *reinterpret_cast<const float4 *>(gb + (long long)r * lddy + c);
+                if (relu) {
+                    d.x = fmaf(a.x, v.x, b.x) > 0.f ? d.x : 0.f; d.y = fmaf(a.y, v.y, b.y) > 0.f ? d.y : 0.f;
+                    d.z = fmaf(a.z, v.z, b.z) > 0.f ? d.z : 0.f; d.w = fmaf(a.w, v.w, b.w) > 0.f ? d.w : 0.f;
                 }
-            } else {
-                const float *cf = coef + (long long)n * 4 * Cp + c;
-                const float4 a = *reinterpret_cast<const float4 *>(cf), b = *reinterpret_cast<const float4 *>(cf + Cp);
-                const float4 rr = *reinterpret_cast<const float4 *>(cf + 2 * Cp), mr = *reinterpret_cast<const float4 *>(cf + 3 * Cp);
-                const float *gb = dy + (long long)n * dys;
-                for (int r = ra + rl; r < rb; r += lanes) {
-                    const float4 v = *reinterpret_cast<const float4 *>(xb + (long long)r * ldx + c);
-                    float4 d = *reinterpret_cast<const float4 *>(gb + (long long)r * lddy + c);
-                    if (relu) {
-                        d.x = fmaf(a.x, v.x, b.x) > 0.f ? d.x : 0.f; d.y = fmaf(a.y, v.y, b.y) > 0.f ? d.y : 0.f;
-                        d.z = fmaf(a.z, v.z, b.z) > 0.f ? d.z : 0.f; d.w = fmaf(a.w, v.w, b.w) > 0.f ? d.w : 0.f;
-                    }
-                    t0.x += d.x; t0.y += d.y; t0.z += d.z; t0.w += d.w;
-                    t1.x = fmaf(d.x, fmaf(v.x, rr.x, -mr.x), t1.x); t1.y = fmaf(d.y, fmaf(v.y, rr.y, -mr.y), t1.y);
-                    t1.z = fmaf(d.z, fmaf(v.z, rr.z, -mr.z), t1.z); t1.w = fmaf(d.w, fmaf(v.w, rr.w, -mr.w), t1.w);
-                }
+                t0.x += d.x; t0.y += d.y; t0.z += d.z; t0.w += d.w;
+                t1.x = fmaf(d.x, fmaf(v.x, rr.x, -mr.x), t1.x); t1.y = fmaf(d.y, fmaf(v.y, rr.y, -mr.y), t1.y);
+                t1.z = fmaf(d.z, fmaf(v.z, rr.z, -mr.z), t1.z); t1.w = fmaf(d.w, fmaf(v.w, rr.w, -mr.w), t1.w);
             }
         }
 #pragma unroll
@@ -117,7 +161,7 @@ __global__ __launch_bounds__(256) void gn_partial_kernel(const float *x, long lo
 
 // block = one (sample, group); thread = (channel of the group, chunk lane).  Sums the chunk partials of every channel
 // in float64, combines the channels of the group, writes stats (mean, rstd) and the per-channel coefficients.
-__global__ __launch_bounds__(256) void gn_final_kernel(const float *part, int chunks, const float *x, long long xs,
+__global__ __launch_bounds__(256) void gn_final_kernel(const double *part, int chunks, const float *x, long long xs,
                                                        const float *gamma, const float *beta, float eps, int G, int V, int C,
                                                        float *stats, float *coef) {
     __shared__ double sS[256], sQ[256];
@@ -132,9 +176,9 @@ __global__ __launch_bounds__(256) void gn_final_kernel(const float *part, int ch
     if (cc < Cg) {
         const int c = g * Cg + cc;
         for (int k = cl; k < chunks; k += CL) {
-            const float *pp = part + ((long long)n * chunks + k) * 2 * Cp;
-            S += (double)pp[c];
-            Q += (double)pp[Cp + c];
+            const double *pp = part + ((long long)n * chunks + k) * 2 * Cp;
+            S += pp[c];
+            Q += pp[Cp + c];
         }
     }
     sS[threadIdx.x] = S; sQ[threadIdx.x] = Q;
@@ -210,12 +254,15 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const float *x, long long
     }
 }
 
+// most rows of a block of the rows form: it runs for every c4 that is no power of two, so c4 >= 3 and 256 / c4 <= 85
+constexpr int GN_ROWS_MAX = 85;
+
 // The same pass with WHOLE ROWS per block (256 / c4 rows, thread = one quad as above): for channel counts whose quads are no
 // power-of-two lane group (the GraphCMR blocks normalise [features | condition]: 288, 544 channels) the row bound goes through
 // an LDS maximum (non-negative floats order like their bit patterns; a NaN's pattern is above every finite one).  c4 <= 256.
 __global__ __launch_bounds__(256) void gn_apply_rows_kernel(const float *x, long long xs, int ldx, const float *coef, int relu,
                                                             float *y, long long ys, int ldy, int N, int V, int C, float *rm) {
-    __shared__ unsigned mx[64];
+    __shared__ unsigned mx[GN_ROWS_MAX];
     const int Cp = (C + 3) & ~3, c4 = Cp >> 2;
     const int RB = 256 / c4, rl = threadIdx.x / c4;
     const long long rows = (long long)N * V;
@@ -335,7 +382,7 @@ __global__ __launch_bounds__(256) void gn_bwd_apply_rows_kernel(const float *x, 
                                                                 int lddy, const float *coef, const float *bcoef, int relu, float *dx,
                                                                 long long dxs, int lddx, const float *add, long long adds, int ldadd,
                                                                 int N, int V, int C, float *rm) {
-    __shared__ unsigned mx[64];
+    __shared__ unsigned mx[GN_ROWS_MAX];
     const int Cp = (C + 3) & ~3, c4 = Cp >> 2;
     const int RB = 256 / c4, rl = threadIdx.x / c4;
     const long long rows = (long long)N * V;
@@ -427,7 +474,7 @@ extern "C" int64_t cape_groupnorm_workspace_bytes(int32_t N, int32_t V, int32_t 
     if (N < 1 || V < 1 || C < 1) return CAPE_EINVAL;
     const int RB = gn_rows(N, V);
     const long long chunks = (V + RB - 1) / RB;
-    return (int64_t)N * chunks * 2 * ((C + 3) & ~3) * (int64_t)sizeof(float);
+    return (int64_t)N * chunks * 2 * ((C + 3) & ~3) * (int64_t)sizeof(double);      // the forward's partials; the backward's are float
 }
 
 extern "C" int cape_groupnorm_fwd(const float *x, int64_t x_sample_stride, int32_t ldx, const float *gamma,
@@ -438,14 +485,15 @@ extern "C" int cape_groupnorm_fwd(const float *x, int64_t x_sample_stride, int32
         ldx < C || ldy < C)
         return CAPE_EINVAL;
     if (!gn_shape_ok(C, G) || !gn_aligned(x, x_sample_stride, ldx) || !gn_aligned(y, y_sample_stride, ldy)) return CAPE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return CAPE_EINVAL;
     if (workspace_bytes < cape_groupnorm_workspace_bytes(N, V, C)) return CAPE_EWORKSPACE;
     const int RB = gn_rows(N, V);
     const int chunks = (V + RB - 1) / RB;
     hipStream_t st = (hipStream_t)stream;
-    CAPE_LAUNCH(gn_partial_kernel<0>, dim3(N * chunks), dim3(256), 0, st, x, (long long)x_sample_stride, ldx, (const float *)nullptr,
-                0LL, 0, (const float *)nullptr, 0, V, C, RB, chunks, (float *)workspace);
+    CAPE_LAUNCH(gn_stat_partial_kernel, dim3(N * chunks), dim3(256), 0, st, x, (long long)x_sample_stride, ldx, V, C, RB, chunks,
+                (double *)workspace);
     CAPE_LAUNCH_CHECK();
-    CAPE_LAUNCH(gn_final_kernel, dim3(N * G), dim3(256), 0, st, (const float *)workspace, chunks, x, (long long)x_sample_stride,
+    CAPE_LAUNCH(gn_final_kernel, dim3(N * G), dim3(256), 0, st, (const double *)workspace, chunks, x, (long long)x_sample_stride,
                 gamma, beta, eps, G, V, C, stats, coef);
     CAPE_LAUNCH_CHECK();
     const bool rows_form = rowmax_out && !gn_rm_fused(C) && C <= 1024;
@@ -472,11 +520,12 @@ extern "C" int cape_groupnorm_bwd(const float *x, int64_t x_sample_stride, int32
     if (!gn_shape_ok(C, G) || !gn_aligned(x, x_sample_stride, ldx) || !gn_aligned(dy, dy_sample_stride, lddy) ||
         !gn_aligned(dx, dx_sample_stride, lddx) || (dx_add && !gn_aligned(dx_add, add_sample_stride, ldadd)))
         return CAPE_EINVAL;
+    if (reinterpret_cast<uintptr_t>(workspace) & 15) return CAPE_EINVAL;
     if (workspace_bytes < cape_groupnorm_workspace_bytes(N, V, C)) return CAPE_EWORKSPACE;
     const int RB = gn_rows(N, V);
     const int chunks = (V + RB - 1) / RB;
     hipStream_t st = (hipStream_t)stream;
-    CAPE_LAUNCH(gn_partial_kernel<1>, dim3(N * chunks), dim3(256), 0, st, x, (long long)x_sample_stride, ldx, dy,
+    CAPE_LAUNCH(gn_partial_kernel, dim3(N * chunks), dim3(256), 0, st, x, (long long)x_sample_stride, ldx, dy,
                 (long long)dy_sample_stride, lddy, coef, relu, V, C, RB, chunks, (float *)workspace);
     CAPE_LAUNCH_CHECK();
     CAPE_LAUNCH(gn_bwd_final_kernel, dim3(N * G), dim3(256), 0, st, (const float *)workspace, chunks, gamma, stats, G, V, C,

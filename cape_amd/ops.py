@@ -1951,6 +1951,7 @@ class GroupNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, G, eps, relu, passthrough=False, g_gamma=None, g_beta=None):
         _lib.require_gpu()
+        ctx.set_materialize_grads(False)         # an unused output's gradient arrives as None, not as zeros (backward's shortcut)
         x = as_act(x)
         assert x.dtype == torch.float32, "group norm reads fp32 activations"
         N, V, Cn = x.shape

@@ -568,14 +568,21 @@ int cape_reduce_cond(const float *dy, int64_t dy_sample_stride, int32_t lddy, co
  * Group norm over [C/G, V] per sample (lib/models.py:681-712: G = min(32, C) chosen by the caller, population variance,
  * eps inside the sqrt) with per-channel gamma / beta and an optional fused ReLU (:751-760):
  *   y = relu?( (x - mean_{n,g}) * rstd_{n,g} * gamma_c + beta_c )
- * Every pass reads whole rows (float4): requires C % 4 == 0 and 16-byte aligned, 4-float-padded views.
- * Outputs kept for the backward pass: stats [N, G, 2] = (mean, rstd) and coef [N, 4, C] = (a = rstd*gamma,
- * b = beta - mean*a, rstd, mean*rstd) per channel; the forward evaluates y = relu?(fma(a, x, b)) and the backward
- * re-derives the ReLU mask from the same fma, so it never reads y.  Statistics: one pass of pivot-shifted sums
- * (pivot = the sample's first row), combined per group in float64.  workspace >= cape_groupnorm_workspace_bytes.
+ * Every pass reads whole rows (float4): any C >= 1 with C / G <= 256, in 16-byte aligned views whose rows are padded to whole
+ * quads (base pointers on 16 bytes, every ld and sample stride a multiple of 4, hence ld >= round_up(C, 4)).  The last quad of
+ * a row loads its pad lanes, which must be readable; their values are never used and never written.
+ * Outputs kept for the backward pass: stats [N, G, 2] = (mean, rstd) and coef [N, 4, round_up(C, 4)] = (a = rstd*gamma,
+ * b = beta - mean*a, rstd, mean*rstd) per channel -- the per-channel tables have the stride round_up(C, 4), their pad lanes
+ * are never written; the forward evaluates y = relu?(fma(a, x, b)) and the backward re-derives the ReLU mask from the same
+ * fma, so it never reads y.  Statistics: one pass of pivot-shifted sums (pivot = the sample's first row) in float64 from the
+ * difference on, so that a first row far from the group's mean costs no accuracy.
+ * workspace: 16-byte aligned, >= cape_groupnorm_workspace_bytes (float64 partials of the forward; the backward needs half).
  * rowmax_out: NULL or [N*V][4] floats that receive the row bounds (max_c |y|, 0, 0, 0) of the output -- of dx in the backward
- * -- for the fp16 two-piece contractions that read it next (cape_gconv_fwd_h2): written by the apply pass itself when a row is
- * a power-of-two lane group (C <= 256, C/4 a power of two), by a wave-per-row form of the same pass otherwise.
+ * -- for the fp16 two-piece contractions that read it next (cape_gconv_fwd_h2), for any C: written by the apply pass itself
+ * when a row is a power-of-two lane group (C <= 256, round_up(C, 4) / 4 a power of two), by a form of the same pass that gives
+ * each block whole rows (256 / (round_up(C, 4) / 4) of them) for any other C <= 1024, by cape_rowmax after the pass above
+ * that.  The bound is defined for rows of finite values: a NaN in a row may be dropped from its bound (lane-group form and
+ * cape_rowmax: fmaxf) or become it (rows-per-block form: the maximum of the bit patterns); an infinity always becomes it.
  */
 int64_t cape_groupnorm_workspace_bytes(int32_t N, int32_t V, int32_t C);
 int cape_groupnorm_fwd(const float *x, int64_t x_sample_stride, int32_t ldx, const float *gamma,
@@ -584,8 +591,8 @@ int cape_groupnorm_fwd(const float *x, int64_t x_sample_stride, int32_t ldx, con
                        int32_t C, void *workspace, int64_t workspace_bytes, float *rowmax_out, void *stream);
 /* dx (+ dx_add when not NULL: a second gradient of the same input -- the residual branch of res_block_decoder,
  * lib/models.py:744-774 -- summed in the apply pass instead of by a separate element-wise launch) plus per-sample partial
- * parameter gradients dgamma_partial / dbeta_partial [N, C] (the caller sums them over N); stats / coef are the forward
- * outputs; bcoef is a [N, 3, round_up(C, 4)] scratch buffer. */
+ * parameter gradients dgamma_partial / dbeta_partial [N, C] (dense; the caller sums them over N); stats / coef are the forward
+ * outputs; bcoef is a [N, 3, round_up(C, 4)] scratch buffer (A_c = rstd*gamma_c, B_g, C_g: dx = A d' - (B + xhat C)). */
 int cape_groupnorm_bwd(const float *x, int64_t x_sample_stride, int32_t ldx, const float *dy,
                        int64_t dy_sample_stride, int32_t lddy, const float *gamma,
                        const float *stats, const float *coef, int32_t G, int32_t relu, float *dx,

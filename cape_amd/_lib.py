@@ -132,6 +132,7 @@ SIGNATURES = {
     "cape_bwd_prep_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
     "cape_bwd_prep": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _i64, _i32, _p, _p, _i32, _p, _i32, _p,
                                 _i64, _i32, _i32, _i32, _i32, _p, _i64, _p, _p]),
+    "cape_bwd_prep_plan": (C.c_int, [_p, _i64, _i32, _p, _i64, _i32, _i32, _p, _p, _i64, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)]),
     "cape_bwd_prep_finalize": (C.c_int, [C.c_void_p, _i32, _p]),
     "cape_spmm": (C.c_int, [_p, _i64, _i32, _p, _p, _p, _i32, _i32, _f32, _p, _i64, _i32, _f32, _p, _i64, _i32,
                             _i32, _i32, _i32, _p, _p]),
@@ -224,7 +225,7 @@ SIGNATURES = {
 }
 
 # bf16-storage variants with the argument list of their fp32 namesake (include/cape_hip.h, last section)
-for _name in ("cape_bwd_prep", "cape_spmm", "cape_spmm_multi", "cape_spmm_combine"):
+for _name in ("cape_bwd_prep", "cape_bwd_prep_plan", "cape_spmm", "cape_spmm_multi", "cape_spmm_combine"):
     SIGNATURES[_name + "_bf16"] = SIGNATURES[_name]
 SIGNATURES["cape_colsum_vertex_bf16"] = (C.c_int, [_p, _i64, _i32, _i32, _i32, _i32, _i32, _p, _p])
 

@@ -750,6 +750,52 @@ extern "C" int64_t cape_bwd_prep_workspace_bytes(int32_t N, int32_t Mo, int32_t 
 }
 
 namespace {
+// The dispatch of cape_bwd_prep, decided on the host from the views alone (cape_bwd_prep_plan returns it as it stands).
+struct BpPlan {
+    int family, depth, RB, chunks, passes, bound;
+};
+template <typename T>
+BpPlan bp_plan(const T *g, int64_t g_sample_stride, int32_t ldg, const T *y, int64_t y_sample_stride, int32_t ldy, int32_t act,
+               const uint32_t *mask, const T *dz, int64_t dz_sample_stride, int32_t lddz, int32_t N, int32_t Mo, int32_t F, bool want_rm) {
+    constexpr int es = (int)sizeof(T);
+    BpPlan P;
+    P.RB = bp_rows(N, Mo);
+    P.chunks = (Mo + P.RB - 1) / P.RB;
+    const bool vec = aligned4(g, g_sample_stride, ldg, F, es) && aligned4(dz, dz_sample_stride, lddz, F, es) &&
+                     (mask || act == CAPE_ACT_NONE || aligned4(y, y_sample_stride, ldy, F, es)) &&
+                     (F >= 256 ? (F % 256) == 0 : (256 % (F / 4)) == 0) && ((F & 31) == 0 || !mask);
+    // 8 channels per thread where the rows allow it (column passes of 512 channels; F / 8 column groups must divide 256)
+    const bool wide = vec && spmm_wide() && aligned8(g, g_sample_stride, ldg, F, es) && aligned8(dz, dz_sample_stride, lddz, F, es) &&
+                      (mask || act == CAPE_ACT_NONE || aligned8(y, y_sample_stride, ldy, F, es)) &&
+                      F >= 256 && (F >= 512 ? (F % 512) == 0 : (256 % (F / 8)) == 0);
+    // measured (tools/bench_sparse.py, profiles/r02_ubench_sparse_bwd_prep.txt): two rows ahead is the best depth for the 4-wide
+    // kernel; the 8-wide one pays only from 256 channels (fewer row lanes per column group below that), fp32 without
+    // read-ahead (167 registers at depth 4, 129 at 2)
+    const int ur = (wide && es == 4) ? 1 : CAPE_BP_UNROLL_DEFAULT;
+    P.family = wide ? CAPE_BP_VEC8 : vec ? CAPE_BP_VEC4 : F <= 4 ? CAPE_BP_NARROW : CAPE_BP_GENERIC;
+    P.depth = vec ? (ur >= 4 ? 4 : ur >= 2 ? 2 : 1) : 0;
+    const int fb = wide ? 512 : vec ? 256 : P.family == CAPE_BP_NARROW ? 4 : 64;
+    P.passes = (F + fb - 1) / fb;
+    // bwd_prep_vec_kernel keeps one bound entry per column pass and a row has four: wider rows, and the scalar forms (which
+    // do not own whole rows per lane group), take the standalone pass
+    P.bound = !want_rm ? CAPE_BP_BOUND_NONE : (vec && P.passes <= 4) ? CAPE_BP_BOUND_KERNEL : CAPE_BP_BOUND_STANDALONE;
+    return P;
+}
+
+template <typename T>
+int bwd_prep_plan_impl(const T *g, int64_t g_sample_stride, int32_t ldg, const T *y, int64_t y_sample_stride, int32_t ldy,
+                       int32_t act, const uint32_t *mask, const T *dz, int64_t dz_sample_stride, int32_t lddz, int32_t N, int32_t Mo,
+                       int32_t F, int32_t want_rowmax, int32_t plan[6]) {
+    if (!plan || (want_rowmax && sizeof(T) != 4)) return CAPE_EINVAL;
+    if (!g || !dz || N < 1 || Mo < 1 || F < 1 || ldg < F || lddz < F) return CAPE_EINVAL;
+    if (act < CAPE_ACT_NONE || act > CAPE_ACT_TANH) return CAPE_EINVAL;
+    if (!mask && act != CAPE_ACT_NONE && (!y || ldy < F)) return CAPE_EINVAL;
+    const BpPlan P = bp_plan<T>(g, g_sample_stride, ldg, y, y_sample_stride, ldy, act, mask, dz, dz_sample_stride, lddz, N, Mo, F,
+                                want_rowmax != 0);
+    plan[0] = P.family; plan[1] = P.depth; plan[2] = P.RB; plan[3] = P.chunks; plan[4] = P.passes; plan[5] = P.bound;
+    return CAPE_OK;
+}
+
 template <typename T>
 int bwd_prep_impl(const T *g, int64_t g_sample_stride, int32_t ldg, const T *y, int64_t y_sample_stride,
                   int32_t ldy, int32_t act, const uint32_t *mask, T *dz, int64_t dz_sample_stride, int32_t lddz,
@@ -764,25 +810,23 @@ int bwd_prep_impl(const T *g, int64_t g_sample_stride, int32_t ldg, const T *y, 
     if ((R > 0 || dcoef_g) && !rowscale) return CAPE_EINVAL;
     if (R > 0 && !dcoef) return CAPE_EINVAL;
     if (workspace_bytes < cape_bwd_prep_workspace_bytes(N, Mo, F, R)) return CAPE_EWORKSPACE;
-    const int RB = bp_rows(N, Mo);
-    const int chunks = (Mo + RB - 1) / RB;
+    const BpPlan P = bp_plan<T>(g, g_sample_stride, ldg, y, y_sample_stride, ldy, act, mask, dz, dz_sample_stride, lddz, N, Mo, F,
+                                rowmax_out != nullptr);
+    const int RB = P.RB, chunks = P.chunks;
+    const bool vec = P.family >= CAPE_BP_VEC4, wide = P.family == CAPE_BP_VEC8;
+    const int bp_ur = P.depth;
     CViewT<T> gv{g, g_sample_stride, ldg}, yv{y, y_sample_stride, ldy};
     ViewT<T> zv{dz, dz_sample_stride, lddz};
     hipStream_t st = (hipStream_t)stream;
-    const bool vec = aligned4(g, g_sample_stride, ldg, F, es) && aligned4(dz, dz_sample_stride, lddz, F, es) &&
-                     (mask || act == CAPE_ACT_NONE || aligned4(y, y_sample_stride, ldy, F, es)) &&
-                     (F >= 256 ? (F % 256) == 0 : (256 % (F / 4)) == 0) && ((F & 31) == 0 || !mask);
-    // 8 channels per thread where the rows allow it (column passes of 512 channels; F / 8 column groups must divide 256)
-    const bool wide = vec && spmm_wide() && aligned8(g, g_sample_stride, ldg, F, es) && aligned8(dz, dz_sample_stride, lddz, F, es) &&
-                      (mask || act == CAPE_ACT_NONE || aligned8(y, y_sample_stride, ldy, F, es)) &&
-                      F >= 256 && (F >= 512 ? (F % 512) == 0 : (256 % (F / 8)) == 0);
-    // measured (tools/bench_sparse.py, profiles/r02_ubench_sparse_bwd_prep.txt): two rows ahead is the best depth for the 4-wide
-    // kernel; the 8-wide one pays only from 256 channels (fewer row lanes per column group below that), fp32 without
-    // read-ahead (167 registers at depth 4, 129 at 2)
-    const int bp_ur = (wide && es == 4) ? 1 : CAPE_BP_UNROLL_DEFAULT;
+    float *rm_kernel = P.bound == CAPE_BP_BOUND_KERNEL ? rowmax_out : nullptr;
+    if (P.bound == CAPE_BP_BOUND_STANDALONE) {
+        // the rows of g as they are on entry (dz may alias g): before the pass below
+        const int rc = rm_standalone(g, g_sample_stride, ldg, N, Mo, F, rowmax_out, stream);
+        if (rc) return rc;
+    }
 #define CAPE_BP_LAUNCH(VW_, UR_)                                                                                                    \
     CAPE_LAUNCH((bwd_prep_vec_kernel<T, VW_, UR_>), dim3(N * chunks), dim3(256), 0, st, gv, yv, act, mask, zv, rowscale, R, rg,     \
-                dbias ? 1 : 0, dcoef_g ? 1 : 0, N, Mo, F, (float *)workspace, chunks, RB, rowmax_out)
+                dbias ? 1 : 0, dcoef_g ? 1 : 0, N, Mo, F, (float *)workspace, chunks, RB, rm_kernel)
     if (vec && wide) {
         if (bp_ur >= 4) CAPE_BP_LAUNCH(8, 4);
         else if (bp_ur >= 2) CAPE_BP_LAUNCH(8, 2);
@@ -800,10 +844,6 @@ int bwd_prep_impl(const T *g, int64_t g_sample_stride, int32_t ldg, const T *y, 
         CAPE_LAUNCH((bwd_prep_kernel<T>), dim3(N * chunks), dim3(256), 0, st, gv, yv, act, mask, zv, rowscale, R, rg, dbias ? 1 : 0,
                     dcoef_g ? 1 : 0, N, Mo, F, (float *)workspace, chunks, RB);
     CAPE_LAUNCH_CHECK();
-    if (rowmax_out && !vec) {                                  // the scalar form does not own whole rows per lane group
-        const int rc = rm_standalone(dz, dz_sample_stride, lddz, N, Mo, F, rowmax_out, stream);
-        if (rc) return rc;
-    }
     if (finalize && (dbias || R > 0 || dcoef_g)) {
         const int fblocks = (F + 15) / 16;
         const int nblk = fblocks * (1 + N * (R + 1));
@@ -834,6 +874,20 @@ extern "C" int cape_bwd_prep_bf16(const void *g, int64_t g_sample_stride, int32_
     return bwd_prep_impl<cape_bf16>((const cape_bf16 *)g, g_sample_stride, ldg, (const cape_bf16 *)y, y_sample_stride, ldy, act, mask,
                                     (cape_bf16 *)dz, dz_sample_stride, lddz, dbias, rowscale, R, dcoef, rg, dcoef_g,
                                     dcoef_sample_stride, finalize, N, Mo, F, workspace, workspace_bytes, rowmax_out, stream);
+}
+
+extern "C" int cape_bwd_prep_plan(const float *g, int64_t g_sample_stride, int32_t ldg, const float *y, int64_t y_sample_stride,
+                                  int32_t ldy, int32_t act, const uint32_t *mask, const float *dz, int64_t dz_sample_stride,
+                                  int32_t lddz, int32_t N, int32_t Mo, int32_t F, int32_t want_rowmax, int32_t plan[6]) {
+    return bwd_prep_plan_impl<float>(g, g_sample_stride, ldg, y, y_sample_stride, ldy, act, mask, dz, dz_sample_stride, lddz, N, Mo, F,
+                                     want_rowmax, plan);
+}
+
+extern "C" int cape_bwd_prep_plan_bf16(const void *g, int64_t g_sample_stride, int32_t ldg, const void *y, int64_t y_sample_stride,
+                                       int32_t ldy, int32_t act, const uint32_t *mask, const void *dz, int64_t dz_sample_stride,
+                                       int32_t lddz, int32_t N, int32_t Mo, int32_t F, int32_t want_rowmax, int32_t plan[6]) {
+    return bwd_prep_plan_impl<cape_bf16>((const cape_bf16 *)g, g_sample_stride, ldg, (const cape_bf16 *)y, y_sample_stride, ldy, act, mask,
+                                         (const cape_bf16 *)dz, dz_sample_stride, lddz, N, Mo, F, want_rowmax, plan);
 }
 
 extern "C" int cape_bwd_prep_finalize(const cape_bwd_prep_item_t *items, int32_t nitems, void *stream) {

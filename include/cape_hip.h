@@ -73,7 +73,7 @@
 extern "C" {
 #endif
 
-#define CAPE_ABI_VERSION 17
+#define CAPE_ABI_VERSION 18
 #define CAPE_MAX_SRC 8
 
 /* error codes (negative = argument error; positive values are hipError_t) */
@@ -372,6 +372,15 @@ int cape_gconv_dw_plan(const cape_src_t *srcs, int32_t nsrc, const float *dz, in
  * [N, R+1, F] buffer, the layout cape_cond_coef_bwd reads); 0 = contiguous (R*F and F).
  * dz may alias g (in place); with act = CAPE_ACT_NONE and mask = NULL an aliased dz is not even stored (dz IS g: the call
  * is made for its sums).  Deterministic two-stage reductions; workspace >= cape_bwd_prep_workspace_bytes.
+ * The terms of dbias and dcoef are the float32 values g * act'(y) BEFORE they are rounded to the storage type of dz (they differ
+ * from the stored dz in bf16 storage only); the terms of dcoef_g are g.  Sums in float32, fixed order.
+ * rowmax_out (fp32 storage only; CAPE_EINVAL with bf16): NULL or [N, Mo, 4].  It bounds the rows of g AS THEY ARE ON ENTRY, in
+ * every form -- and therefore the rows of dz too (|act'| <= 1 and the mask is 0 / 1, so |dz| <= |g| element by element); the
+ * caller may attach it to both tensors.  Entry p of a row is max |g[n, r, c]| over the columns of column pass p (256 channels
+ * per pass with four channels per thread, 512 with eight) where the vector kernel writes it in its own launch: the views are
+ * vector-eligible and the row has at most four passes (F <= 1024 / 2048).  Every other form (the generic and the narrow kernel,
+ * more than four passes) takes one standalone pass over g before the launch: entry 0 = max over the whole row.  Entries that no
+ * pass owns are +0; the bound of a row is the maximum over its four entries.
  */
 int64_t cape_bwd_prep_workspace_bytes(int32_t N, int32_t Mo, int32_t F, int32_t R);
 int cape_bwd_prep(const float *g, int64_t g_sample_stride, int32_t ldg, const float *y,
@@ -379,6 +388,23 @@ int cape_bwd_prep(const float *g, int64_t g_sample_stride, int32_t ldg, const fl
                   int64_t dz_sample_stride, int32_t lddz, float *dbias, const float *rowscale,
                   int32_t R, float *dcoef, int32_t rg, float *dcoef_g, int64_t dcoef_sample_stride, int32_t finalize,
                   int32_t N, int32_t Mo, int32_t F, void *workspace, int64_t workspace_bytes, float *rowmax_out, void *stream);
+
+/* What cape_bwd_prep launches for these views, decided on the host without a launch (the function cape_bwd_prep itself
+ * decides by; same refusals of the view arguments).  want_rowmax: whether rowmax_out would be non-NULL.  plan[0] = family
+ * (CAPE_BP_*), plan[1] = rows a thread loads ahead (1, 2 or 4; 0 for the generic and the narrow kernel), plan[2] = rows per
+ * block RB, plan[3] = chunks per sample = ceil(Mo / RB) (the grid is N * chunks; the final stage sums N * chunks partials per
+ * bias column), plan[4] = column passes (of 64 / F / 256 / 512 channels), plan[5] = how the row bound is produced
+ * (CAPE_BP_BOUND_*).  The kernel tests use it to prove that every form is reached by a comparison against float64. */
+#define CAPE_BP_GENERIC 0
+#define CAPE_BP_NARROW 1           /* F <= 4: one row per thread */
+#define CAPE_BP_VEC4 2             /* four channels per thread */
+#define CAPE_BP_VEC8 3             /* eight channels per thread */
+#define CAPE_BP_BOUND_NONE 0
+#define CAPE_BP_BOUND_KERNEL 1
+#define CAPE_BP_BOUND_STANDALONE 2
+int cape_bwd_prep_plan(const float *g, int64_t g_sample_stride, int32_t ldg, const float *y, int64_t y_sample_stride,
+                       int32_t ldy, int32_t act, const uint32_t *mask, const float *dz, int64_t dz_sample_stride, int32_t lddz,
+                       int32_t N, int32_t Mo, int32_t F, int32_t want_rowmax, int32_t plan[6]);
 
 /* finalize = 0 above leaves the reductions as partial slabs in the workspace; this entry finishes up to
  * CAPE_MAX_BWD_PREP_ITEMS of them in ONE launch (same N, Mo, F, R and destinations as the deferred calls, whose
@@ -419,7 +445,7 @@ int cape_spmm(const float *x, int64_t x_sample_stride, int32_t ldx, const int32_
 #define CAPE_MAX_SPMM_TERMS 4
 /* rowmax_out (cape_spmm, cape_spmm_multi in sum mode, cape_spmm_combine, cape_bwd_prep; fp32 storage only): NULL or
  * [N, Mo, 4]: the bound of max_c |out[n, r, c]| of the row the call writes (y / dz; cape_bwd_prep bounds its INPUT g, which
- * bounds dz as well), as cape_h2_src_t.rowmax with
+ * bounds dz as well: see there), as cape_h2_src_t.rowmax with
  * rowmax_w = 4 -- written by the same kernel where the lanes of a row form one power-of-two group, by a standalone pass
  * (cape_rowmax) inside the call otherwise. */
 typedef struct cape_spmm_term {
@@ -834,6 +860,9 @@ int cape_bwd_prep_bf16(const void *g, int64_t g_sample_stride, int32_t ldg, cons
                        float *dbias, const float *rowscale, int32_t R, float *dcoef, int32_t rg, float *dcoef_g,
                        int64_t dcoef_sample_stride, int32_t finalize, int32_t N, int32_t Mo, int32_t F, void *workspace,
                        int64_t workspace_bytes, float *rowmax_out, void *stream);
+int cape_bwd_prep_plan_bf16(const void *g, int64_t g_sample_stride, int32_t ldg, const void *y, int64_t y_sample_stride,
+                            int32_t ldy, int32_t act, const uint32_t *mask, const void *dz, int64_t dz_sample_stride, int32_t lddz,
+                            int32_t N, int32_t Mo, int32_t F, int32_t want_rowmax, int32_t plan[6]);
 /* out[m, c] (+)= sum_n x[n, m, c]: gradient of the per-vertex output bias [1, M, F] (lib/models.py:615) from a bf16 dz */
 int cape_colsum_vertex_bf16(const void *x, int64_t x_sample_stride, int32_t ldx, int32_t N, int32_t M, int32_t C,
                             int32_t accumulate, float *out, void *stream);

@@ -13,11 +13,11 @@ V = 6890
 ENTRIES = ("cape_vertex_error", "cape_error_stats_workspace_bytes", "cape_error_stats")
 
 
-def test_header_names_the_entries_and_abi_is_17():
+def test_header_names_the_entries_and_abi_is_18():
     from cape_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "cape_hip.h")).read()
-    assert int(re.search(r"#define CAPE_ABI_VERSION (\d+)", hdr).group(1)) == 17
-    assert _lib.lib.cape_abi_version() == 17
+    assert int(re.search(r"#define CAPE_ABI_VERSION (\d+)", hdr).group(1)) == 18
+    assert _lib.lib.cape_abi_version() == 18
     for name in ENTRIES:
         assert re.search(r"^\s*(?:int|int64_t)\s+%s\s*\(" % name, hdr, flags=re.M), name
         assert name in _lib.SIGNATURES and hasattr(_lib.lib, name)

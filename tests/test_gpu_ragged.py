@@ -133,6 +133,8 @@ def test_spmm_empty_rows_and_axpby():
 
 
 def test_bwd_prep_ragged():
+    """Three shapes of the generic kernel through the wrapper; every form, operand and edge of the backward-prep kernels is held
+    to float64 (dz bit for bit) by tests/test_gpu_bwd_prep.py."""
     from cape_amd import ops
     dev = torch.device("cuda:0")
     rng = np.random.default_rng(9)

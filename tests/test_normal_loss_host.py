@@ -150,11 +150,11 @@ def test_lambda_normal_needs_three_channels(make_model):
 
 # ---- C-ABI ---------------------------------------------------------------------------------------------------------------
 
-def test_abi_version_17():
+def test_abi_version_18():
     from cape_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "cape_hip.h")).read()
-    assert int(re.search(r"#define CAPE_ABI_VERSION (\d+)", hdr).group(1)) == 17
-    assert _lib.lib.cape_abi_version() == 17
+    assert int(re.search(r"#define CAPE_ABI_VERSION (\d+)", hdr).group(1)) == 18
+    assert _lib.lib.cape_abi_version() == 18
     assert "cape_face_normal_loss_fwd_bwd" in hdr and "cape_face_normal_loss_workspace_bytes" in hdr
 
 

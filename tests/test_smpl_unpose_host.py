@@ -120,7 +120,7 @@ def test_the_entries_are_declared_bound_and_leave_the_abi_version_alone():
     for name in ("cape_smpl_unpose_workspace_bytes", "cape_smpl_unpose_joints", "cape_smpl_unpose_skin", "cape_smpl_undress"):
         assert re.search(r"^\s*(?:int|int64_t)\s+%s\s*\(" % name, hdr, flags=re.M), name
         assert name in _lib.SIGNATURES and hasattr(_lib.lib, name)
-    assert _lib.lib.cape_abi_version() == 17
+    assert _lib.lib.cape_abi_version() == 18
 
 
 def test_unpose_entry_points_reject_bad_arguments_before_launching():

@@ -1810,7 +1810,60 @@ class CAPE(base_model):
         if lambda_edge:
             _, ed, vptr, vidx = self._edge_tables()
             no_ref = torch.zeros((V, 3), dtype=torch.float32, device=self.device)
-        res = dict(z=[], pose=[], transl=[], posed=[], clothed=[], loss=[], normal=[])
+
+        def data_term(begin, end):
+            nb = end - begin
+            tgt = self._padded(target, begin, end)
+            loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
+            grad = torch.zeros((bs, V, 3), dtype=torch.float32, device=self.device)       # padded rows stay zero
+            if lambda_vnormal:
+                # w_v n_v(target) / sum w in fp64 (the term's value is summed in fp64), padded rows zero; the term's
+                # gradient to the posed normals is -lambda_vnormal times that, the same at every step
+                with torch.no_grad():
+                    tnw = body.vertex_normals(tgt).double() * (w_dev.double() * inv_wsum)[None, :, None]
+                    tnw[nb:] = 0.0
+                    g_normal = (-lambda_vnormal * tnw).float()
+                normal = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
+
+            def term(step, posed, want_grad):
+                smpl_mod.weighted_l2(posed, tgt, w_dev, inv_wsum, nb, loss[step], grad if want_grad else None)
+                roots, seeds = [posed], [grad]
+                if lambda_vnormal:
+                    nrm = body.vertex_normals_diff(posed) if want_grad else body.vertex_normals(posed)
+                    # sum_v w_v / sum w = 1: the term is 1 - sum_v w_v n_v . n_v(target) / sum w
+                    normal[step, :nb] = (1.0 - (nrm.detach().double() * tnw).sum((1, 2)))[:nb].float()
+                if lambda_edge and want_grad:
+                    # the batch mean of the training loss's edge term, scaled back to a sum over the samples
+                    e_total, _ = ops.ReconEdgeLossFn.apply(posed[:nb], tgt[:nb], no_ref, ed, vptr, vidx, 0.0,
+                                                           float(lambda_edge) * nb)
+                    roots.append(e_total)
+                    seeds.append(None)
+                if lambda_vnormal:
+                    roots.append(nrm)
+                    seeds.append(g_normal)
+                return roots, seeds
+
+            def results():
+                out = dict(loss=loss[:, :nb].cpu().numpy())
+                if lambda_vnormal:
+                    out['normal'] = normal[:, :nb].cpu().numpy()
+                return out
+
+            return term, results
+
+        return self._fit_leaves(size, body, dressing, z0, cond, cond2, pose, transl, steps, lr, lambda_z, optimize_pose,
+                                optimize_transl, data_term)
+
+    def _fit_leaves(self, size, body, dressing, z0, cond, cond2, pose, transl, steps, lr, lambda_z, optimize_pose, optimize_transl,
+                    data_term):
+        """fit_posed's and fit_scan's batch loop: Adam on the leaves ``z`` (and ``pose`` / ``transl``) of
+        decoder -> ``dressing.diff`` -> ``body.forward_diff`` per padded batch, with the model's variables frozen and its
+        gradient buckets out of reach, and a last evaluation of the returned leaves as ``decode_posed`` evaluates them.
+        ``data_term(begin, end)`` returns per batch (term, results): ``term(step, posed, want_grad)`` records the step's values
+        and returns the (roots, seeds) of the one backward call; ``results()`` the batch's per-sample arrays [steps + 1, nb] by
+        name.  Arguments as ``_posed_arguments`` returns them; the device pass is open."""
+        bs, nz = self.batch_size, int(self.nz)
+        res = dict(z=[], pose=[], transl=[], posed=[], clothed=[])
         # the model's variables are constants here: no gradient bucket to write into and, while the steps run, nothing that
         # requires a gradient (the ops then skip their weight-gradient kernels)
         grad_views, self._grad_views = self._grad_views, {}
@@ -1824,51 +1877,26 @@ class CAPE(base_model):
             for begin, end in self._batches(size):
                 nb = end - begin
                 # one condition row stands for every sample, in the valid rows only: the batches decode_posed feeds the decoder
-                z, bc, bc2, bp, tgt = (self._padded(a, begin, end) for a in (z0, cond, cond2, pose, target))
+                z, bc, bc2, bp = (self._padded(a, begin, end) for a in (z0, cond, cond2, pose))
                 z.requires_grad_(True)
                 bp.requires_grad_(bool(optimize_pose))
                 bt = None if transl is None else self._padded(transl, begin, end).requires_grad_(bool(optimize_transl))
                 leaves = [z] + ([bp] if optimize_pose else []) + ([bt] if optimize_transl else [])
                 opt = torch.optim.Adam(leaves, lr=float(lr))
-                loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
-                grad = torch.zeros((bs, V, 3), dtype=torch.float32, device=self.device)       # padded rows stay zero
-                if lambda_vnormal:
-                    # w_v n_v(target) / sum w in fp64 (the term's value is summed in fp64), padded rows zero; the term's
-                    # gradient to the posed normals is -lambda_vnormal times that, the same at every step
-                    with torch.no_grad():
-                        tnw = body.vertex_normals(tgt).double() * (w_dev.double() * inv_wsum)[None, :, None]
-                        tnw[nb:] = 0.0
-                        g_normal = (-lambda_vnormal * tnw).float()
-                    normal = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
+                term, results = data_term(begin, end)
 
                 def evaluate(step, want_grad):
                     with self.variable_scope('generator'):
                         x = self.decoder_cond_vert(torch.cat([z, bc, bc2], 1), bc, bc2, use_res_block=self.use_res_block_dec)
                     T = dressing.diff(x.float().contiguous())
                     posed, _ = body.forward_diff(T, bp, None, bt)
-                    smpl_mod.weighted_l2(posed, tgt, w_dev, inv_wsum, nb, loss[step], grad if want_grad else None)
-                    nrm = None
-                    if lambda_vnormal:
-                        nrm = body.vertex_normals_diff(posed) if want_grad else body.vertex_normals(posed)
-                        # sum_v w_v / sum w = 1: the term is 1 - sum_v w_v n_v . n_v(target) / sum w
-                        normal[step, :nb] = (1.0 - (nrm.detach().double() * tnw).sum((1, 2)))[:nb].float()
-                    return T, posed, nrm
+                    return (T, posed) + tuple(term(step, posed, want_grad))
 
                 freeze(True)
                 try:
                     for step in range(steps):
-                        T, posed, nrm = evaluate(step, True)
+                        T, posed, roots, seeds = evaluate(step, True)
                         opt.zero_grad(set_to_none=True)
-                        roots, seeds = [posed], [grad]
-                        if lambda_edge:
-                            # the batch mean of the training loss's edge term, scaled back to a sum over the samples
-                            e_total, _ = ops.ReconEdgeLossFn.apply(posed[:nb], tgt[:nb], no_ref, ed, vptr, vidx, 0.0,
-                                                                   float(lambda_edge) * nb)
-                            roots.append(e_total)
-                            seeds.append(None)
-                        if lambda_vnormal:
-                            roots.append(nrm)
-                            seeds.append(g_normal)
                         torch.autograd.backward(roots, seeds)
                         if lambda_z:
                             z.grad.add_(z.detach(), alpha=2.0 * float(lambda_z) / nz)
@@ -1876,20 +1904,88 @@ class CAPE(base_model):
                 finally:
                     freeze(False)
                 with torch.no_grad():            # the returned leaves as decode_posed evaluates them, kernel for kernel
-                    T, posed, _ = evaluate(steps, False)
+                    T, posed, _, _ = evaluate(steps, False)
                 res['z'].append(z.detach()[:nb].cpu().numpy())
                 res['pose'].append(bp.detach()[:nb].cpu().numpy())
                 res['transl'].append(None if bt is None else bt.detach()[:nb].cpu().numpy())
                 res['posed'].append(posed[:nb].cpu().numpy())
                 res['clothed'].append(T[:nb].cpu().numpy())
-                res['loss'].append(loss[:, :nb].cpu().numpy())
-                if lambda_vnormal:
-                    res['normal'].append(normal[:, :nb].cpu().numpy())
+                for k, a in results().items():
+                    res.setdefault(k, []).append(a)
         finally:
             self._grad_views = grad_views
         cat = lambda k, ax=0: np.concatenate(res[k], ax)
         out = dict(z=cat('z'), pose=cat('pose'), transl=None if transl is None else cat('transl'), posed=cat('posed'),
-                   clothed=cat('clothed'), loss=cat('loss', 1))
-        if lambda_vnormal:
-            out['normal'] = cat('normal', 1)
+                   clothed=cat('clothed'))
+        for k in res:
+            if k not in out:
+                out[k] = cat(k, 1)
         return out
+
+    def fit_scan(self, scan, pose, cond, cond2, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None, z0=None,
+                 steps=200, lr=0.1, lambda_z=0.0, optimize_pose=False, optimize_transl=False, max_dist=None):
+        """``fit_posed`` for raw scans -- points without correspondence: gradient descent (Adam) on ``z`` through
+        decoder -> cape_smpl_dress -> SMPL posing -> scan-to-mesh distance (``SMPL.scan_distance_diff``: for every scan point
+        the closest point of the posed surface, searched over all faces on the device at every step).
+
+        ``scan`` a [size, M, 3] array, or a list of ``size`` arrays [m_n, 3] with m_n >= 1; everything else as in
+        ``fit_posed``, which this shares its loop with.  Per sample the objective is
+
+            (1 / m_n) sum_i [d2_i <= max_dist^2] d2_i  +  lambda_z mean(z^2)
+
+        with d2_i the squared distance of scan point i to the posed mesh.  ``max_dist`` (metres; None: no truncation) drops the
+        points farther than that from the current mesh: the mask comes from each step's forward and is a constant of that
+        step's gradient.  Points without a finite distance (a non-finite coordinate) are dropped likewise.
+
+        Returns a dict: ``z``, ``pose``, ``transl``, ``posed``, ``clothed`` as ``fit_posed`` returns them, ``loss``
+        [steps + 1, size] the data term per sample (row 0: before the first update; the last row for the returned leaves) and
+        ``inliers`` [steps + 1, size], the number of points under the mask."""
+        from .scan_distance import pad_points
+        body = getattr(body_model, 'model', body_model)
+        pts, count = pad_points(scan)
+        size, M, V, bs, nz = pts.shape[0], pts.shape[1], body.V, self.batch_size, int(self.nz)
+        if count is None:
+            count = np.full(size, M, np.int32)
+        if max_dist is not None:
+            max_dist = float(max_dist)
+            if not max_dist >= 0.0:
+                raise ValueError("max_dist must be >= 0 or None, got %r" % (max_dist,))
+        if transl is None and optimize_transl:
+            transl = np.zeros((size, 3), np.float32)
+        _, pose, transl, dressing, cond, cond2 = self._posed_arguments(size, body, pose, transl,
+                                                                       (mean, std, clothing_idx, minimal_shape), cond, cond2)
+        z0 = np.zeros((size, nz), np.float32) if z0 is None else np.asarray(z0, dtype=np.float32)
+        if z0.shape != (size, nz):
+            raise ValueError("z0: [%d, %d] expected" % (size, nz))
+        steps = int(steps)
+        limit = float('inf') if max_dist is None else max_dist * max_dist
+        self._open_pass()
+
+        def data_term(begin, end):
+            nb = end - begin
+            p = self._padded(pts, begin, end)
+            cnt = np.zeros(bs, np.int32)                                                  # padded rows: no points
+            cnt[:nb] = count[begin:end]
+            counts = body._scan_distance().counts(cnt, bs, M)                             # checked and uploaded once
+            cnt_dev = counts[1]
+            inv_m = (1.0 / torch.as_tensor(np.maximum(cnt, 1)).to(self.device).double())[:, None]
+            valid = torch.arange(M, device=self.device)[None, :] < cnt_dev[:, None]
+            loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
+            inliers = torch.zeros((steps + 1, bs), dtype=torch.int32, device=self.device)
+
+            def term(step, posed, want_grad):
+                d2 = body.scan_distance_diff(posed, p, counts) if want_grad else body.scan_distance(posed, p, counts)[0]
+                d = d2.detach()
+                mask = valid & (d <= limit)                                               # a NaN distance is no inlier
+                md = mask.double()
+                loss[step] = ((d.double() * md).nan_to_num_(nan=0.0).sum(1, keepdim=True) * inv_m)[:, 0].float()
+                inliers[step] = mask.sum(1).int()
+                return [d2], [(md * inv_m).float()]
+
+            def results():
+                return dict(loss=loss[:, :nb].cpu().numpy(), inliers=inliers[:, :nb].cpu().numpy())
+
+            return term, results
+
+        return self._fit_leaves(size, body, dressing, z0, cond, cond2, pose, transl, steps, lr, lambda_z, optimize_pose,
+                                optimize_transl, data_term)

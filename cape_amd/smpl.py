@@ -10,6 +10,8 @@ bodies (reference demos.py:155-161, 207-213 and :249-331, which go through ``smp
                              (cape_smpl_unpose_joints / cape_smpl_unpose_skin); ``unpose_np`` on numpy arrays
   SMPL.vertex_normals(...)   per-vertex normals of meshes in the model's topology (``cape_amd.vertex_normals`` on the model's
                              ``faces``); ``vertex_normals_diff`` with a gradient, ``vertex_normals_np`` on numpy arrays
+  SMPL.scan_distance(...)    squared distance and closest point of raw scan points to meshes in the model's topology
+                             (``cape_amd.scan_distance``); ``scan_distance_diff`` with a gradient, ``scan_distance_np`` on numpy
   dress(...)                 de-normalise + clothing mask + minimal body (cape_smpl_dress)
   undress(...)               its right-inverse: rest body -> normalised displacements (cape_smpl_undress)
   dress_diff(...)            the same with a gradient to the displacements (cape_smpl_dress_bwd)
@@ -148,6 +150,7 @@ class SMPL(object):
                             jt_colptr=(tp, np.int32), jt_rowidx=(ti, np.int32), jt_vals=(jt.data, np.float32))
         self._dev = None
         self._normals = None
+        self._scan = None
         self._parents_c = (C.c_int32 * J)(*[int(x) for x in self.parents])
 
     @property
@@ -383,6 +386,27 @@ class SMPL(object):
     def vertex_normals_np(self, verts):
         """``vertex_normals``, numpy in, numpy out."""
         return self._vertex_normals().np(verts)
+
+    def _scan_distance(self):
+        """``ScanDistance`` on the model's own ``faces``, validated and uploaded on first use."""
+        if self._scan is None:
+            from .scan_distance import ScanDistance
+            self._scan = ScanDistance(self.faces, self.V, device=self._device)
+        return self._scan
+
+    def scan_distance(self, verts, points, count=None, out=None):
+        """(d2 [N, M], face [N, M], bary [N, M, 3]): for every device scan point ``points`` [N, M, 3] the squared distance to,
+        and the closest point on, the device meshes ``verts`` [N, V, 3] in the model's topology, as
+        ``cape_amd.scan_distance.ScanDistance.forward`` computes them (no gradient)."""
+        return self._scan_distance().forward(verts, points, count, out)
+
+    def scan_distance_diff(self, verts, points, count=None):
+        """``scan_distance``'s d2 as an autograd function: gradients on it flow to ``verts`` and ``points``."""
+        return self._scan_distance().diff(verts, points, count)
+
+    def scan_distance_np(self, verts, points):
+        """``scan_distance``, numpy in (``points`` an array or a list of [m_n, 3] arrays), numpy out."""
+        return self._scan_distance().np(verts, points)
 
     def pose(self, verts, pose, betas=None, transl=None):
         """numpy in, numpy out: (vertices [N,V,3], joints [N,J,3]) float32."""

@@ -63,6 +63,10 @@
  *   cape_vertex_normals_fwd / cape_vertex_normals_bwd
  *                       lib/losses.py:54-80 estimate_vertex_normals on lib/utils.py:119-135 TriNormals / NormalizedNx3 (never
  *                       called by the reference) for a batch of meshes, and its gradient w.r.t. the vertices.
+ *   cape_scan_nearest_fwd / cape_scan_nearest_bwd
+ *                       no counterpart in the reference, which only sees registered data: for every point of a raw scan the
+ *                       closest point of a batch of meshes (the rule of cape_amd/mesh_operators.py:_closest_on_triangles, over
+ *                       all faces), and the gradient of the squared distance w.r.t. the vertices and the points.
  */
 #ifndef CAPE_HIP_H
 #define CAPE_HIP_H
@@ -1102,6 +1106,47 @@ int cape_vertex_normals_fwd(const float *x, int32_t ldx, const int32_t *faces, c
 int cape_vertex_normals_bwd(const float *x, int32_t ldx, const float *gnormals, int32_t ldg, const int32_t *faces,
                             const int32_t *vert_face_ptr, const int32_t *vert_face_idx, int32_t N, int32_t V, int32_t F, float *dx,
                             int32_t ldd, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * Scan-to-mesh distance (cape_amd/csrc/scan/scan_distance.hip): for every scan point the closest point of a triangle mesh, for
+ * a batch of meshes that share one topology.  x [N, V, 3] with leading dimension ldx >= 3 (pad never read), samples V rows
+ * apart; faces [F, 3] int32 vertex indices in [0, V); points [N, M, 3] with leading dimension ldp >= 3 (pad never read),
+ * samples M rows apart; count [N] int32 ON THE DEVICE, how many of a sample's M rows are points (values outside [0, M] are
+ * clamped), or NULL: all M.  Per sample n and point i < count[n], with (a, b, c) the corners of face f in x[n]:
+ *   foot(p, f) = the closest point of triangle f to p by the seven-region rule of mesh_operators._closest_on_triangles
+ *                (interior, edges ab / bc / ca, vertices a / b / c; the first test that holds wins)
+ *   d2(p, f) = |p - foot|^2;   face[n, i] = argmin_f d2(p, f), the lowest index among equal fp32 values
+ * A face whose evaluation is not finite never wins.  No finite face, or a point with a non-finite coordinate: face -1, d2 NaN,
+ * bary 0.  Padding rows i >= count[n]: face -1, d2 0, bary 0 (their points are never read).  Outputs, all contiguous:
+ * face [N, M] int32, bary [N, M, 3] (foot = sum_k bary_k x[faces[face, k]]), d2 [N, M].
+ * Three launches: one 64-byte record per (sample, face) in sample-local fp32 coordinates (x[n, 0] subtracted in fp64: the
+ * sample's first vertex must be finite); the exact fp32 search over all faces, records streamed through LDS, the best kept with
+ * a strict `<` in increasing face order, the faces split over plan[0] workgroups per tile of plan[2] points when the grid
+ * would be small; the merge of the parts in increasing order (the result of the unsplit walk) and the evaluation of the winner
+ * in fp64 from the original coordinates: fp32 in and out, fp64 in between.  The same inputs give the same bits.
+ * cape_scan_distance_plan: plan[0] = the split, a function of (N, F, M) only; plan[1] = faces per LDS tile; plan[2] = points
+ * per workgroup.  cape_scan_distance_workspace_bytes(N, V, F, M): what either entry needs (16-byte aligned, no initialisation).
+ *
+ * cape_scan_nearest_bwd: for the seed g [N, M] = d L / d d2 and a forward's face / bary,
+ *   dx[n, v] = sum over the points i whose face has v as corner k, in point order, of g_i (-2 bary_ik (p_i - foot_i))
+ *   dp[n, i] = 2 g_i (p_i - foot_i)                                              (dp NULL: not wanted)
+ * the exact gradient of d2 wherever it is differentiable (the selection and the region are constants: the envelope theorem).
+ * dx [N, V, 3] (leading dimension ldd >= 3, pad never written) is overwritten, not accumulated; dp [N, M, 3] (lddp >= 3,
+ * likewise).  Points with face < 0 (or >= F) add nothing and get dp = 0.  Two launches: per point its corner ids, the
+ * coefficients -2 g bary_k and p - foot in fp64 into the workspace; then one work item per (sample, vertex) walks the sample's
+ * points in order and sums in fp64.  No atomics: the same inputs give the same bits.
+ * Errors: CAPE_EINVAL for NULL operands (count and dp may be NULL), N, V, F, M < 1, a leading dimension below 3, N M, N V or
+ * 3 F >= 2^31, a workspace that is short or not 16-byte aligned; all decided before any launch.  The contents of faces, face
+ * and count are the caller's to validate.
+ */
+int64_t cape_scan_distance_workspace_bytes(int32_t N, int32_t V, int32_t F, int32_t M);
+int cape_scan_distance_plan(int32_t N, int32_t F, int32_t M, int32_t *plan);
+int cape_scan_nearest_fwd(const float *x, int32_t ldx, const int32_t *faces, const float *points, int32_t ldp,
+                          const int32_t *count, int32_t N, int32_t V, int32_t F, int32_t M, int32_t *face, float *bary, float *d2,
+                          void *workspace, int64_t workspace_bytes, void *stream);
+int cape_scan_nearest_bwd(const float *x, int32_t ldx, const int32_t *faces, const float *points, int32_t ldp,
+                          const int32_t *face, const float *bary, const float *g, int32_t N, int32_t V, int32_t F, int32_t M,
+                          float *dx, int32_t ldd, float *dp, int32_t lddp, void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

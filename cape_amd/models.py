@@ -1923,7 +1923,8 @@ class CAPE(base_model):
         return out
 
     def fit_scan(self, scan, pose, cond, cond2, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None, z0=None,
-                 steps=200, lr=0.1, lambda_z=0.0, optimize_pose=False, optimize_transl=False, max_dist=None):
+                 steps=200, lr=0.1, lambda_z=0.0, optimize_pose=False, optimize_transl=False, max_dist=None, lambda_mesh=0.0,
+                 mesh_weights=None, mesh_max_dist=None):
         """``fit_posed`` for raw scans -- points without correspondence: gradient descent (Adam) on ``z`` through
         decoder -> cape_smpl_dress -> SMPL posing -> scan-to-mesh distance (``SMPL.scan_distance_diff``: for every scan point
         the closest point of the posed surface, searched over all faces on the device at every step).
@@ -1937,15 +1938,40 @@ class CAPE(base_model):
         points farther than that from the current mesh: the mask comes from each step's forward and is a constant of that
         step's gradient.  Points without a finite distance (a non-finite coordinate) are dropped likewise.
 
+        That term alone pulls every scan point's closest surface point and nothing else: it cannot see a part of the surface
+        that no scan point chose.  ``lambda_mesh > 0`` adds the opposite, mesh-to-scan term (``SMPL.point_distance_diff``;
+        DESIGN 7j), which makes the objective two-sided (chamfer):
+
+            +  lambda_mesh  sum_v w_v [e2_v <= mesh_max_dist^2] e2_v / sum_v w_v
+
+        with e2_v the squared distance of posed vertex v to the nearest of the sample's scan points, searched over all points
+        on the device at every step, and w ``mesh_weights`` [V] (None: ones; a positive sum is required).  The term samples
+        the mesh AT ITS VERTICES (about 1 cm apart on SMPL), not on the face interiors.  ``mesh_max_dist`` (metres; None: no
+        truncation) drops the vertices farther than that from the scan -- what a partial scan needs; the mask comes from each
+        step's forward and is a constant of that step's gradient, and a distance that is NaN is dropped.  The scan is a
+        constant: no gradient to its points is computed.  With ``lambda_mesh = 0`` nothing of this runs.
+
         Returns a dict: ``z``, ``pose``, ``transl``, ``posed``, ``clothed`` as ``fit_posed`` returns them, ``loss``
-        [steps + 1, size] the data term per sample (row 0: before the first update; the last row for the returned leaves) and
-        ``inliers`` [steps + 1, size], the number of points under the mask."""
+        [steps + 1, size] the scan-to-mesh term per sample (row 0: before the first update; the last row for the returned
+        leaves) and ``inliers`` [steps + 1, size], the number of points under the mask; with ``lambda_mesh > 0`` also
+        ``mesh_loss`` [steps + 1, size], the mesh-to-scan term before the multiplication by ``lambda_mesh``, and
+        ``mesh_inliers`` [steps + 1, size], the number of vertices with a positive weight under its mask."""
         from .scan_distance import pad_points
+        lambda_mesh = float(lambda_mesh)
+        if not np.isfinite(lambda_mesh) or lambda_mesh < 0:
+            raise ValueError("lambda_mesh must be finite and >= 0, got %r" % (lambda_mesh,))
+        if mesh_max_dist is not None:
+            mesh_max_dist = float(mesh_max_dist)
+            if not mesh_max_dist >= 0.0:
+                raise ValueError("mesh_max_dist must be >= 0 or None, got %r" % (mesh_max_dist,))
         body = getattr(body_model, 'model', body_model)
         pts, count = pad_points(scan)
         size, M, V, bs, nz = pts.shape[0], pts.shape[1], body.V, self.batch_size, int(self.nz)
         if count is None:
             count = np.full(size, M, np.int32)
+        mw = np.ones(V, np.float32) if mesh_weights is None else np.asarray(mesh_weights, dtype=np.float32)
+        if mw.shape != (V,) or not float(mw.astype(np.float64).sum()) > 0.0:
+            raise ValueError("mesh_weights: [%d] with a positive sum expected" % V)
         if max_dist is not None:
             max_dist = float(max_dist)
             if not max_dist >= 0.0:
@@ -1959,7 +1985,12 @@ class CAPE(base_model):
             raise ValueError("z0: [%d, %d] expected" % (size, nz))
         steps = int(steps)
         limit = float('inf') if max_dist is None else max_dist * max_dist
+        mesh_limit = float('inf') if mesh_max_dist is None else mesh_max_dist * mesh_max_dist
         self._open_pass()
+        if lambda_mesh:
+            mw_dev = self._dev(mw).double()[None]
+            mw_pos = self._dev(mw)[None] > 0
+            inv_mwsum = 1.0 / float(mw.astype(np.float64).sum())
 
         def data_term(begin, end):
             nb = end - begin
@@ -1972,6 +2003,9 @@ class CAPE(base_model):
             valid = torch.arange(M, device=self.device)[None, :] < cnt_dev[:, None]
             loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
             inliers = torch.zeros((steps + 1, bs), dtype=torch.int32, device=self.device)
+            if lambda_mesh:
+                mesh_loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
+                mesh_inliers = torch.zeros((steps + 1, bs), dtype=torch.int32, device=self.device)
 
             def term(step, posed, want_grad):
                 d2 = body.scan_distance_diff(posed, p, counts) if want_grad else body.scan_distance(posed, p, counts)[0]
@@ -1980,10 +2014,24 @@ class CAPE(base_model):
                 md = mask.double()
                 loss[step] = ((d.double() * md).nan_to_num_(nan=0.0).sum(1, keepdim=True) * inv_m)[:, 0].float()
                 inliers[step] = mask.sum(1).int()
-                return [d2], [(md * inv_m).float()]
+                roots, seeds = [d2], [(md * inv_m).float()]
+                if lambda_mesh:
+                    # the same checked counts: a padded row has none, its vertices come back NaN and are dropped
+                    e2 = body.point_distance_diff(posed, p, counts) if want_grad else body.point_distance(posed, p, counts)[0]
+                    e = e2.detach()
+                    near = e <= mesh_limit                                                # a NaN distance is no inlier
+                    wm = near.double() * mw_dev
+                    mesh_loss[step] = ((e.double() * wm).nan_to_num_(nan=0.0).sum(1) * inv_mwsum).float()
+                    mesh_inliers[step] = (near & mw_pos).sum(1).int()
+                    roots.append(e2)
+                    seeds.append((wm * (lambda_mesh * inv_mwsum)).float())
+                return roots, seeds
 
             def results():
-                return dict(loss=loss[:, :nb].cpu().numpy(), inliers=inliers[:, :nb].cpu().numpy())
+                out = dict(loss=loss[:, :nb].cpu().numpy(), inliers=inliers[:, :nb].cpu().numpy())
+                if lambda_mesh:
+                    out.update(mesh_loss=mesh_loss[:, :nb].cpu().numpy(), mesh_inliers=mesh_inliers[:, :nb].cpu().numpy())
+                return out
 
             return term, results
 

@@ -12,6 +12,8 @@ bodies (reference demos.py:155-161, 207-213 and :249-331, which go through ``smp
                              ``faces``); ``vertex_normals_diff`` with a gradient, ``vertex_normals_np`` on numpy arrays
   SMPL.scan_distance(...)    squared distance and closest point of raw scan points to meshes in the model's topology
                              (``cape_amd.scan_distance``); ``scan_distance_diff`` with a gradient, ``scan_distance_np`` on numpy
+  SMPL.point_distance(...)   the opposite direction: squared distance of every vertex to the nearest raw scan point
+                             (``cape_amd.point_distance``); ``point_distance_diff`` with a gradient, ``point_distance_np`` on numpy
   dress(...)                 de-normalise + clothing mask + minimal body (cape_smpl_dress)
   undress(...)               its right-inverse: rest body -> normalised displacements (cape_smpl_undress)
   dress_diff(...)            the same with a gradient to the displacements (cape_smpl_dress_bwd)
@@ -151,6 +153,7 @@ class SMPL(object):
         self._dev = None
         self._normals = None
         self._scan = None
+        self._point = None
         self._parents_c = (C.c_int32 * J)(*[int(x) for x in self.parents])
 
     @property
@@ -407,6 +410,27 @@ class SMPL(object):
     def scan_distance_np(self, verts, points):
         """``scan_distance``, numpy in (``points`` an array or a list of [m_n, 3] arrays), numpy out."""
         return self._scan_distance().np(verts, points)
+
+    def _point_distance(self):
+        """``PointDistance`` on the model's device, constructed on first use."""
+        if self._point is None:
+            from .point_distance import PointDistance
+            self._point = PointDistance(device=self._device)
+        return self._point
+
+    def point_distance(self, verts, points, count=None, out=None):
+        """(d2 [N, V], index [N, V] int32): for every vertex of ``verts`` [N, V, 3] the squared distance to the nearest of
+        ``points`` [N, M, 3] (``count`` [N]: how many rows of a sample are points) and that point's index, as
+        ``cape_amd.point_distance.PointDistance.forward`` computes them (no gradient)."""
+        return self._point_distance().forward(verts, points, count, out)
+
+    def point_distance_diff(self, verts, points, count=None):
+        """``point_distance``'s d2 as an autograd function: gradients on it flow to ``verts`` and ``points``."""
+        return self._point_distance().diff(verts, points, count)
+
+    def point_distance_np(self, verts, points):
+        """``point_distance``, numpy in (``points`` an array or a list of [m_n, 3] arrays), numpy out."""
+        return self._point_distance().np(verts, points)
 
     def pose(self, verts, pose, betas=None, transl=None):
         """numpy in, numpy out: (vertices [N,V,3], joints [N,J,3]) float32."""

@@ -9,12 +9,8 @@
 // Forward, two launches.  (1) search, fp32, in the difference form (q - p) on the raw coordinates: the difference of two nearby
 // fp32 numbers is exact, so the rounding scales with the distance, not with the position -- no sample-local origin and no prep
 // launch; the expanded form |q|^2 + |p|^2 - 2 q.p (and with it the matrix pipe) would cancel to a few per cent of a millimetre
-// distance on a metre-sized body.  A workgroup of SB threads holds QB = QPT SB queries of one sample in registers and streams a
-// range of the sample's points through LDS in tiles of PT float4; all lanes read the same point at the same time (one
-// ds_read_b128 broadcast per QPT tests), and the best is kept with a strict `<` in increasing point order.  With few workgroups
-// the points are split over `split` workgroups per query tile (a function of the sizes only); every part writes its
-// (d2 bits, index) candidate.  (2) finish: the candidates are merged in increasing part order with the same strict `<` -- the
-// result of the unsplit walk -- and the winner is evaluated in fp64.
+// distance on a metre-sized body.  The skeleton is nearest.h's: QB = QPT SB queries per workgroup, points through LDS in tiles
+// of PT float4 (one ds_read_b128 broadcast per QPT tests).  (2) finish: nearest.h's merge, the winner evaluated in fp64.
 //
 // QPT = 2: the test is 9 VALU instructions (3 sub, mul, 2 fma, cmp, 2 cndmask), so one LDS read feeds 18 of them.  Measured
 // on an MI355X at Q = 6890, M = 20000 (alternating sets, same bits from all three): 2 / 4 / 8 queries per thread take
@@ -26,44 +22,23 @@
 // wanted -- its negative as three doubles into the workspace.  (2) one thread per (sample, point): workgroups of points stream
 // the sample's indices through LDS in query order and add the record where the index is theirs: fixed-order fp64 sums, the same
 // inputs give the same bits.
-#include "../common.h"
+#include "nearest.h"
 
 namespace {
 
-constexpr int SB = 256;             // threads of a search workgroup
+using namespace nearest;
+
 #ifndef CAPE_POINT_QPT
 #define CAPE_POINT_QPT 2            // a build with another value (make EXTRA=-DCAPE_POINT_QPT=4) is for measuring it only
 #endif
 constexpr int QPT = CAPE_POINT_QPT; // queries per thread
 constexpr int QB = SB * QPT;        // queries per workgroup
 constexpr int PT = 512;             // points per LDS tile (8 KB of float4)
-constexpr int SPLIT_MAX = 16;       // most workgroups that share one query tile's points
 constexpr int TARGET_WG = 1024;     // split until about this many workgroups exist (four per compute unit: one wave per SIMD each)
-constexpr int LB = 256;             // threads of the per-item kernels
-constexpr int MAXB = 4096;
 constexpr int GT = 2048;            // indices per LDS tile of the gather
 constexpr int64_t REC = 3;          // doubles per query of the backward: -2 g (q - p)
 
-struct Plan {
-    int tiles;            // query tiles per sample
-    int split;            // workgroups per query tile
-    int tiles_per_part;   // point tiles each of them walks
-};
-
-// a function of the sizes only
-inline Plan make_plan(int64_t N, int64_t Q, int64_t M) {
-    Plan p;
-    p.tiles = (int)((Q + QB - 1) / QB);
-    const int64_t wg = N * p.tiles;
-    const int64_t ptiles = (M + PT - 1) / PT;
-    int64_t s = TARGET_WG / wg;
-    if (s > SPLIT_MAX) s = SPLIT_MAX;
-    if (s > ptiles) s = ptiles;
-    if (s < 1) s = 1;
-    p.tiles_per_part = (int)((ptiles + s - 1) / s);
-    p.split = (int)((ptiles + p.tiles_per_part - 1) / p.tiles_per_part);
-    return p;
-}
+inline Plan point_plan(int64_t N, int64_t Q, int64_t M) { return make_plan(N, Q, QB, M, PT, TARGET_WG, SPLIT_MAX); }
 
 // work items and indices are int32
 inline bool sizes_ok(int64_t N, int64_t Q, int64_t M) {
@@ -71,104 +46,77 @@ inline bool sizes_ok(int64_t N, int64_t Q, int64_t M) {
     return N >= 1 && Q >= 1 && M >= 1 && N * Q < lim && N * M < lim;
 }
 
-inline int64_t fwd_bytes(int64_t N, int64_t Q, int64_t M) { return (int64_t)make_plan(N, Q, M).split * N * Q * 8; }
+inline int64_t fwd_bytes(int64_t N, int64_t Q, int64_t M) { return cand_bytes(N, Q, point_plan(N, Q, M)); }
 inline int64_t bwd_bytes(int64_t N, int64_t Q) { return N * Q * REC * 8; }
 
-__device__ __forceinline__ int clamp_count(const int *count, long long n, int M) {
-    if (!count) return M;
-    const int c = count[n];
-    return c < 0 ? 0 : (c > M ? M : c);
-}
-
 // ---- forward (1): the fp32 search ------------------------------------------------------------------------------------------------
-// grid: N * split * tiles workgroups, the query tile fastest.  cand [split][N Q] (d2 bits, index), written for every query: a part
-// whose range lies beyond count[n] writes (inf, -1).
+// raw queries against raw points in the difference form; every query gets a candidate, (inf, -1) from a part beyond count[n]
+struct PointSearch {
+    static constexpr int QPT = ::QPT, TILE = PT, REC = 1, UNROLL = 4;
+    using Row = long long;                                                  // M + PT may pass 2^31
+    struct Args {
+        const float *q;
+        int ldq;
+        const float *pts;
+        int ldp, Q, M;
+    };
+    static __device__ __forceinline__ void load_query(const Args &a, long long n, int j, float &qx, float &qy, float &qz) {
+        const float *s = a.q + (n * a.Q + j) * a.ldq;
+        qx = s[0];
+        qy = s[1];
+        qz = s[2];
+    }
+    static __device__ __forceinline__ void stage(const Args &a, float4 *tile, long long n, int i0, int np) {
+        for (int i = threadIdx.x; i < np; i += SB) {
+            const float *s = a.pts + (n * a.M + i0 + i) * a.ldp;
+            tile[i] = make_float4(s[0], s[1], s[2], 0.0f);
+        }
+    }
+    static __device__ __forceinline__ float d2(float qx, float qy, float qz, const float4 (&p)[1]) {
+        const float dx = qx - p[0].x, dy = qy - p[0].y, dz = qz - p[0].z;
+        return __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx));               // never a NaN or an inf wins the strict `<`
+    }
+};
+
 __global__ __launch_bounds__(SB) void point_search_kernel(const float *q, int ldq, const float *pts, int ldp, const int *count,
                                                           int Q, int M, int tiles, int split, int tiles_per_part, long long NQ,
                                                           uint2 *cand) {
     __shared__ float4 tile[PT];
-    const int t = blockIdx.x % tiles;
-    const int part = (blockIdx.x / tiles) % split;
     const long long n = blockIdx.x / (tiles * split);
-    const int cnt = clamp_count(count, n, M);
-    const int j0 = t * QB;
-    float qx[QPT], qy[QPT], qz[QPT], best[QPT];
-    int bi[QPT];
-#pragma unroll
-    for (int k = 0; k < QPT; ++k) {
-        const int j = j0 + k * SB + threadIdx.x;
-        qx[k] = qy[k] = qz[k] = 0.0f;
-        if (j < Q) {
-            const float *s = q + (n * Q + j) * ldq;
-            qx[k] = s[0];
-            qy[k] = s[1];
-            qz[k] = s[2];
-        }
-        best[k] = __builtin_inff();
-        bi[k] = -1;
-    }
-    const long long i_begin = (long long)part * tiles_per_part * PT;       // a range of the M rows: the split never looks at count
-    const long long i_stop = i_begin + (long long)tiles_per_part * PT;
-    const int i_end = (int)(i_stop < cnt ? i_stop : cnt);                   // padding points are never read
-    for (long long i0l = i_begin; i0l < i_end; i0l += PT) {                 // uniform over the workgroup
-        const int i0 = (int)i0l;
-        const int np = i_end - i0 < PT ? i_end - i0 : PT;
-        __syncthreads();                                                    // the previous tile has been read by every wave
-        for (int i = threadIdx.x; i < np; i += SB) {
-            const float *s = pts + (n * M + i0 + i) * ldp;
-            tile[i] = make_float4(s[0], s[1], s[2], 0.0f);
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int i = 0; i < np; ++i) {
-            const float4 p = tile[i];
-#pragma unroll
-            for (int k = 0; k < QPT; ++k) {
-                const float dx = qx[k] - p.x, dy = qy[k] - p.y, dz = qz[k] - p.z;
-                const float d = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx));
-                if (d < best[k]) {                                          // strict: the lowest point among ties, never a NaN or an inf
-                    best[k] = d;
-                    bi[k] = i0 + i;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < QPT; ++k) {
-        const int j = j0 + k * SB + threadIdx.x;
-        if (j < Q) cand[(long long)part * NQ + n * Q + j] = make_uint2(__float_as_uint(best[k]), (unsigned)bi[k]);
-    }
+    const PointSearch::Args a = {q, ldq, pts, ldp, Q, M};
+    nearest_search<PointSearch>(a, tile, n, Q, Q, clamp_count(count, n, M), tiles, split, tiles_per_part, NQ, cand);
 }
 
-// ---- forward (2): merge and the fp64 evaluation of the winner -------------------------------------------------------------------
-__global__ __launch_bounds__(LB) void point_finish_kernel(const float *q, int ldq, const float *pts, int ldp, const uint2 *cand,
-                                                          int split, int N, int Q, int M, int *index, float *d2) {
-    const long long total = (long long)N * Q;
-    for (long long idx = (long long)blockIdx.x * LB + threadIdx.x; idx < total; idx += (long long)gridDim.x * LB) {
-        const long long n = idx / Q;
-        int id = -1;
-        float best = __builtin_inff();
-        for (int s = 0; s < split; ++s) {                                   // parts hold increasing point ranges
-            const uint2 c = cand[(long long)s * total + idx];
-            const float d = __uint_as_float(c.x);
-            if (d < best) {
-                best = d;
-                id = (int)c.y;
-            }
-        }
+// ---- forward (2): the fp64 evaluation of the winner; none, or one whose fp64 distance is not finite: index -1, d2 NaN -----------
+struct PointFinish {
+    struct Args {
+        const float *q;
+        int ldq;
+        const float *pts;
+        int ldp, M;
+        int *index;
+        float *d2;
+    };
+    static __device__ __forceinline__ void write(const Args &a, long long n, long long idx, bool, int id) {
         float out = __builtin_nanf("");
-        if (id >= 0 && id < M) {
-            const float *a = q + idx * ldq, *b = pts + (n * M + id) * ldp;
-            const double dx = (double)a[0] - (double)b[0], dy = (double)a[1] - (double)b[1], dz = (double)a[2] - (double)b[2];
+        if (id >= 0 && id < a.M) {
+            const float *u = a.q + idx * a.ldq, *v = a.pts + (n * a.M + id) * a.ldp;
+            const double dx = (double)u[0] - (double)v[0], dy = (double)u[1] - (double)v[1], dz = (double)u[2] - (double)v[2];
             const double dd = dx * dx + dy * dy + dz * dz;
             if (isfinite(dd)) out = (float)dd;
             else id = -1;
         } else {
             id = -1;
         }
-        index[idx] = id;
-        d2[idx] = out;
+        a.index[idx] = id;
+        a.d2[idx] = out;
     }
+};
+
+__global__ __launch_bounds__(LB) void point_finish_kernel(const float *q, int ldq, const float *pts, int ldp, const uint2 *cand,
+                                                          int split, int N, int Q, int M, int *index, float *d2) {
+    const PointFinish::Args a = {q, ldq, pts, ldp, M, index, d2};
+    nearest_finish<PointFinish>(a, nullptr, cand, split, N, Q);
 }
 
 // ---- backward (1): per query -----------------------------------------------------------------------------------------------------
@@ -257,7 +205,7 @@ extern "C" int64_t cape_point_distance_workspace_bytes(int32_t N, int32_t Q, int
 
 extern "C" int cape_point_distance_plan(int32_t N, int32_t Q, int32_t M, int32_t *plan) {
     if (!plan || !sizes_ok(N, Q, M)) return CAPE_EINVAL;
-    plan[0] = make_plan(N, Q, M).split;
+    plan[0] = point_plan(N, Q, M).split;
     plan[1] = PT;
     plan[2] = QB;
     return CAPE_OK;
@@ -268,19 +216,21 @@ extern "C" int cape_point_nearest_fwd(const float *q, int32_t ldq, const float *
                                       int64_t workspace_bytes, void *stream) {
     if (!q || !points || !index || !d2 || !workspace) return CAPE_EINVAL;
     if (!sizes_ok(N, Q, M) || ldq < 3 || ldp < 3) return CAPE_EINVAL;
-    if (((uintptr_t)workspace & 15) != 0 || workspace_bytes < fwd_bytes(N, Q, M)) return CAPE_EINVAL;
-    const Plan p = make_plan(N, Q, M);
-    const long long groups = (long long)N * p.split * p.tiles;
-    if (groups >= ((long long)1 << 31)) return CAPE_EINVAL;
+    const Plan p = point_plan(N, Q, M);
+    const long long groups = search_groups(N, p);
+    if (!launch_ok(workspace, workspace_bytes, fwd_bytes(N, Q, M), groups)) return CAPE_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     uint2 *cand = (uint2 *)workspace;
-    CAPE_LAUNCH(point_search_kernel, dim3((unsigned)groups), dim3(SB), 0, st, q, ldq, points, ldp, count, Q, M, p.tiles, p.split,
-                p.tiles_per_part, (long long)N * Q, cand);
-    CAPE_LAUNCH_CHECK();
-    CAPE_LAUNCH(point_finish_kernel, dim3(cape_grid_blocks((long long)N * Q, LB, MAXB)), dim3(LB), 0, st, q, ldq, points, ldp,
-                (const uint2 *)cand, p.split, N, Q, M, index, d2);
-    CAPE_LAUNCH_CHECK();
-    return CAPE_OK;
+    return forward(
+        groups, (long long)N * Q,
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(point_search_kernel, grid, block, 0, st, q, ldq, points, ldp, count, Q, M, p.tiles, p.split,
+                        p.tiles_per_part, (long long)N * Q, cand);
+        },
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(point_finish_kernel, grid, block, 0, st, q, ldq, points, ldp, (const uint2 *)cand, p.split, N, Q, M, index,
+                        d2);
+        });
 }
 
 extern "C" int cape_point_nearest_bwd(const float *q, int32_t ldq, const float *points, int32_t ldp, const int32_t *count,
@@ -289,10 +239,9 @@ extern "C" int cape_point_nearest_bwd(const float *q, int32_t ldq, const float *
                                       void *stream) {
     if (!q || !points || !index || !g || !dq || !workspace) return CAPE_EINVAL;
     if (!sizes_ok(N, Q, M) || ldq < 3 || ldp < 3 || lddq < 3 || (dp && lddp < 3)) return CAPE_EINVAL;
-    if (((uintptr_t)workspace & 15) != 0 || workspace_bytes < bwd_bytes(N, Q)) return CAPE_EINVAL;
     const int ptiles = (M + LB - 1) / LB;
     const long long groups = (long long)N * ptiles;
-    if (groups >= ((long long)1 << 31)) return CAPE_EINVAL;
+    if (!launch_ok(workspace, workspace_bytes, bwd_bytes(N, Q), groups)) return CAPE_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     double *rec = dp ? (double *)workspace : nullptr;
     CAPE_LAUNCH(point_query_grad_kernel, dim3(cape_grid_blocks((long long)N * Q, LB, MAXB)), dim3(LB), 0, st, q, ldq, points, ldp,

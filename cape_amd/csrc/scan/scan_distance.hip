@@ -9,54 +9,29 @@
 // Forward, three launches.  (1) prep: one 64-byte record per (sample, face) in SAMPLE-LOCAL coordinates (x[n, 0] subtracted in
 // fp64, then rounded to fp32: the body's extent, not its position, sets the search's rounding): corner a, edges u = b - a and
 // v = c - a, u.u, u.v, v.v and the reciprocals of u.u, v.v, |c - b|^2 and |u x v|^2 -- every division of the rule has a
-// per-face denominator, so the inner loop has none.  (2) search, fp32: a workgroup of SB threads holds PB = 2 SB points of one
-// sample in registers and streams a range of faces through LDS in tiles of FT records; all lanes read the same record at the same
-// time (an LDS broadcast), regions are chosen by selects, and the best is kept with a strict `<` in increasing face order.  With
-// few workgroups the faces are split over `split` workgroups per point tile (a function of the sizes only); every part writes its
-// (d2 bits, face) candidate.  (3) finish: the candidates are merged in increasing part order with the same strict `<` -- the
-// result of the unsplit walk -- and the winner is evaluated again in fp64 from the original fp32 coordinates: fp32 in and out,
-// fp64 in between.
+// per-face denominator, so the inner loop has none.  (2) search, fp32, nearest.h's skeleton: PB = 2 SB points per workgroup,
+// faces through LDS in tiles of FT records, regions chosen by selects.  (3) finish: nearest.h's merge, and the winner is
+// evaluated again in fp64 from the original fp32 coordinates: fp32 in and out, fp64 in between.
 //
 // Backward, two launches, no atomics.  (1) per point: the corner ids of its face, the coefficients -2 g b_k and r = p - foot
 // (fp64, foot = a + b_1 (b - a) + b_2 (c - a) from the saved barycentrics), and dp = 2 g r when wanted.  (2) one thread per
 // (sample, vertex): workgroups of vertices stream the sample's corner ids through LDS in point order and add coef_k r in fp64
 // where the vertex is a corner: fixed-order sums, the same inputs give the same bits.
-#include "../common.h"
+#include "nearest.h"
 
 namespace {
 
-constexpr int SB = 256;             // threads of a search workgroup
+using namespace nearest;
+
 constexpr int PPT = 2;              // points per thread
 constexpr int PB = SB * PPT;        // points per workgroup
 constexpr int FT = 512;             // faces per LDS tile (32 KB of records)
-constexpr int SPLIT_MAX = 16;       // most workgroups that share one point tile's faces
 constexpr int TARGET_WG = 512;      // split until about this many workgroups exist (two per compute unit)
-constexpr int LB = 256;             // threads of the per-item kernels
-constexpr int MAXB = 4096;
 constexpr int GT = 1024;            // points per LDS tile of the gather
 constexpr int64_t REC_BYTES = 64;   // a face record
 constexpr int64_t PAY = 6;          // doubles per point of the backward: 3 coefficients, r
 
-struct Plan {
-    int tiles;            // point tiles per sample
-    int split;            // workgroups per point tile
-    int tiles_per_part;   // face tiles each of them walks
-};
-
-// a function of the sizes only
-inline Plan make_plan(int64_t N, int64_t F, int64_t M) {
-    Plan p;
-    p.tiles = (int)((M + PB - 1) / PB);
-    const int64_t wg = N * p.tiles;
-    const int64_t ftiles = (F + FT - 1) / FT;
-    int64_t s = TARGET_WG / wg;
-    if (s > SPLIT_MAX) s = SPLIT_MAX;
-    if (s > ftiles) s = ftiles;
-    if (s < 1) s = 1;
-    p.tiles_per_part = (int)((ftiles + s - 1) / s);
-    p.split = (int)((ftiles + p.tiles_per_part - 1) / p.tiles_per_part);
-    return p;
-}
+inline Plan scan_plan(int64_t N, int64_t F, int64_t M) { return make_plan(N, M, PB, F, FT, TARGET_WG, SPLIT_MAX); }
 
 // work items and table entries are int32
 inline bool sizes_ok(int64_t N, int64_t V, int64_t F, int64_t M) {
@@ -64,7 +39,7 @@ inline bool sizes_ok(int64_t N, int64_t V, int64_t F, int64_t M) {
     return N >= 1 && V >= 1 && F >= 1 && M >= 1 && N * M < lim && N * V < lim && 3 * F < lim;
 }
 
-inline int64_t fwd_bytes(int64_t N, int64_t F, int64_t M) { return N * F * REC_BYTES + (int64_t)make_plan(N, F, M).split * N * M * 8; }
+inline int64_t fwd_bytes(int64_t N, int64_t F, int64_t M) { return N * F * REC_BYTES + cand_bytes(N, M, scan_plan(N, F, M)); }
 inline int64_t bwd_bytes(int64_t N, int64_t M) { return N * M * (16 + PAY * 8); }
 
 struct d3 {
@@ -74,12 +49,6 @@ struct d3 {
 __device__ __forceinline__ d3 load3(const float *p) { return {(double)p[0], (double)p[1], (double)p[2]}; }
 __device__ __forceinline__ d3 sub(d3 a, d3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ double dot(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-__device__ __forceinline__ int clamp_count(const int *count, long long n, int M) {
-    if (!count) return M;
-    const int c = count[n];
-    return c < 0 ? 0 : (c > M ? M : c);
-}
 
 // ---- forward (1): face records -------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(LB) void scan_face_record_kernel(const float *x, int ldx, const int *faces, int N, int V, int F,
@@ -143,59 +112,38 @@ __device__ __forceinline__ float tri_d2(float px, float py, float pz, float4 r0,
     return rx * rx + ry * ry + rz * rz;
 }
 
-// grid: N * split * tiles workgroups, the point tile fastest.  cand [split][N M] (d2 bits, face) for the points below count.
+// points in sample-local coordinates against face records; candidates for the points below count only
+struct ScanSearch {
+    static constexpr int QPT = PPT, TILE = FT, REC = 4, UNROLL = 0;
+    using Row = int;                                                        // sizes_ok: 3 F < 2^31
+    struct Args {
+        const float4 *rec;
+        const float *pts;
+        int ldp, F, M;
+        d3 o;                                                               // the sample's origin, x[n, 0]
+    };
+    static __device__ __forceinline__ void load_query(const Args &a, long long n, int i, float &px, float &py, float &pz) {
+        const d3 p = sub(load3(a.pts + (n * a.M + i) * a.ldp), a.o);
+        px = (float)p.x;
+        py = (float)p.y;
+        pz = (float)p.z;
+    }
+    static __device__ __forceinline__ void stage(const Args &a, float4 *tile, long long n, int f0, int nf) {
+        const float4 *src = a.rec + (n * a.F + f0) * 4;
+        for (int j = threadIdx.x; j < nf * 4; j += SB) tile[j] = src[j];
+    }
+    static __device__ __forceinline__ float d2(float px, float py, float pz, const float4 (&r)[4]) {
+        return tri_d2(px, py, pz, r[0], r[1], r[2], r[3]);
+    }
+};
+
 __global__ __launch_bounds__(SB) void scan_search_kernel(const float4 *rec, const float *x, int ldx, const float *pts, int ldp,
                                                          const int *count, int V, int F, int M, int tiles, int split,
                                                          int tiles_per_part, long long NM, uint2 *cand) {
     __shared__ float4 tile[FT * 4];
-    const int t = blockIdx.x % tiles;
-    const int part = (blockIdx.x / tiles) % split;
     const long long n = blockIdx.x / (tiles * split);
-    const int cnt = clamp_count(count, n, M);
-    const int i0 = t * PB;
-    if (i0 >= cnt) return;                                                  // the whole workgroup: no barrier is left waiting
-    const d3 o = load3(x + n * V * ldx);
-    float px[PPT], py[PPT], pz[PPT], best[PPT];
-    int bf[PPT];
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const int i = i0 + k * SB + threadIdx.x;
-        px[k] = py[k] = pz[k] = 0.0f;
-        if (i < cnt) {                                                      // padding points are never read
-            const d3 p = sub(load3(pts + (n * M + i) * ldp), o);
-            px[k] = (float)p.x;
-            py[k] = (float)p.y;
-            pz[k] = (float)p.z;
-        }
-        best[k] = __builtin_inff();
-        bf[k] = -1;
-    }
-    const int f_begin = part * tiles_per_part * FT;                         // below F: split parts are never empty
-    const int f_stop = f_begin + tiles_per_part * FT;
-    const int f_end = f_stop < F ? f_stop : F;
-    for (int f0 = f_begin; f0 < f_end; f0 += FT) {
-        const int nf = f_end - f0 < FT ? f_end - f0 : FT;
-        __syncthreads();                                                    // the previous tile has been read by every wave
-        const float4 *src = rec + (n * F + f0) * 4;
-        for (int j = threadIdx.x; j < nf * 4; j += SB) tile[j] = src[j];
-        __syncthreads();
-        for (int j = 0; j < nf; ++j) {
-            const float4 r0 = tile[4 * j], r1 = tile[4 * j + 1], r2 = tile[4 * j + 2], r3 = tile[4 * j + 3];
-#pragma unroll
-            for (int k = 0; k < PPT; ++k) {
-                const float d = tri_d2(px[k], py[k], pz[k], r0, r1, r2, r3);
-                if (d < best[k]) {                                          // strict: the lowest face among ties, never a NaN
-                    best[k] = d;
-                    bf[k] = f0 + j;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < PPT; ++k) {
-        const int i = i0 + k * SB + threadIdx.x;
-        if (i < cnt) cand[(long long)part * NM + n * M + i] = make_uint2(__float_as_uint(best[k]), (unsigned)bf[k]);
-    }
+    const ScanSearch::Args a = {rec, pts, ldp, F, M, load3(x + n * V * ldx)};
+    nearest_search<ScanSearch>(a, tile, n, M, clamp_count(count, n, M), F, tiles, split, tiles_per_part, NM, cand);
 }
 
 // ---- forward (3): merge and the fp64 evaluation of the winner -------------------------------------------------------------------
@@ -227,32 +175,28 @@ __device__ __forceinline__ double closest_fp64(d3 a, d3 b, d3 c, d3 p, double (&
     return dot(r, r);
 }
 
-__global__ __launch_bounds__(LB) void scan_finish_kernel(const float *x, int ldx, const int *faces, const float *pts, int ldp,
-                                                         const int *count, const uint2 *cand, int split, int N, int V, int M,
-                                                         int *face, float *bary, float *d2) {
-    const long long total = (long long)N * M;
-    for (long long idx = (long long)blockIdx.x * LB + threadIdx.x; idx < total; idx += (long long)gridDim.x * LB) {
-        const int i = (int)(idx % M);
-        const long long n = idx / M;
-        int f = -1;
+// padding rows (i >= count[n]): face -1, d2 0, bary 0; a point without a finite face: face -1, d2 NaN, bary 0
+struct ScanFinish {
+    struct Args {
+        const float *x;
+        int ldx;
+        const int *faces;
+        const float *pts;
+        int ldp, V;
+        int *face;
+        float *bary, *d2;
+    };
+    static __device__ __forceinline__ void write(const Args &a, long long n, long long idx, bool valid, int f) {
         float out_d = 0.0f, out_b[3] = {0.0f, 0.0f, 0.0f};
-        if (i < clamp_count(count, n, M)) {
-            float best = __builtin_inff();
-            for (int s = 0; s < split; ++s) {                               // parts hold increasing face ranges
-                const uint2 c = cand[(long long)s * total + idx];
-                const float d = __uint_as_float(c.x);
-                if (d < best) {
-                    best = d;
-                    f = (int)c.y;
-                }
-            }
+        if (valid) {
             out_d = __builtin_nanf("");
             if (f >= 0) {
-                const float *xs = x + n * V * ldx;
+                const float *xs = a.x + n * a.V * a.ldx;
                 double bw[3];
                 d3 r;
-                const double dd = closest_fp64(load3(xs + (long long)faces[3 * f] * ldx), load3(xs + (long long)faces[3 * f + 1] * ldx),
-                                               load3(xs + (long long)faces[3 * f + 2] * ldx), load3(pts + idx * ldp), bw, r);
+                const double dd = closest_fp64(load3(xs + (long long)a.faces[3 * f] * a.ldx),
+                                               load3(xs + (long long)a.faces[3 * f + 1] * a.ldx),
+                                               load3(xs + (long long)a.faces[3 * f + 2] * a.ldx), load3(a.pts + idx * a.ldp), bw, r);
                 if (isfinite(dd)) {
                     out_d = (float)dd;
 #pragma unroll
@@ -262,11 +206,18 @@ __global__ __launch_bounds__(LB) void scan_finish_kernel(const float *x, int ldx
                 }
             }
         }
-        face[idx] = f;
-        d2[idx] = out_d;
+        a.face[idx] = f;
+        a.d2[idx] = out_d;
 #pragma unroll
-        for (int k = 0; k < 3; ++k) bary[idx * 3 + k] = out_b[k];
+        for (int k = 0; k < 3; ++k) a.bary[idx * 3 + k] = out_b[k];
     }
+};
+
+__global__ __launch_bounds__(LB) void scan_finish_kernel(const float *x, int ldx, const int *faces, const float *pts, int ldp,
+                                                         const int *count, const uint2 *cand, int split, int N, int V, int M,
+                                                         int *face, float *bary, float *d2) {
+    const ScanFinish::Args a = {x, ldx, faces, pts, ldp, V, face, bary, d2};
+    nearest_finish<ScanFinish>(a, count, cand, split, N, M);
 }
 
 // ---- backward (1): point records -------------------------------------------------------------------------------------------------
@@ -350,7 +301,7 @@ extern "C" int64_t cape_scan_distance_workspace_bytes(int32_t N, int32_t V, int3
 
 extern "C" int cape_scan_distance_plan(int32_t N, int32_t F, int32_t M, int32_t *plan) {
     if (!plan || !sizes_ok(N, 1, F, M)) return CAPE_EINVAL;
-    plan[0] = make_plan(N, F, M).split;
+    plan[0] = scan_plan(N, F, M).split;
     plan[1] = FT;
     plan[2] = PB;
     return CAPE_OK;
@@ -361,23 +312,25 @@ extern "C" int cape_scan_nearest_fwd(const float *x, int32_t ldx, const int32_t 
                                      float *d2, void *workspace, int64_t workspace_bytes, void *stream) {
     if (!x || !faces || !points || !face || !bary || !d2 || !workspace) return CAPE_EINVAL;
     if (!sizes_ok(N, V, F, M) || ldx < 3 || ldp < 3) return CAPE_EINVAL;
-    if (((uintptr_t)workspace & 15) != 0 || workspace_bytes < fwd_bytes(N, F, M)) return CAPE_EINVAL;
-    const Plan p = make_plan(N, F, M);
-    const long long groups = (long long)N * p.split * p.tiles;
-    if (groups >= ((long long)1 << 31)) return CAPE_EINVAL;
+    const Plan p = scan_plan(N, F, M);
+    const long long groups = search_groups(N, p);
+    if (!launch_ok(workspace, workspace_bytes, fwd_bytes(N, F, M), groups)) return CAPE_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     float4 *rec = (float4 *)workspace;
     uint2 *cand = (uint2 *)((char *)workspace + (int64_t)N * F * REC_BYTES);
     CAPE_LAUNCH(scan_face_record_kernel, dim3(cape_grid_blocks((long long)N * F, LB, MAXB)), dim3(LB), 0, st, x, ldx, faces, N, V, F,
                 rec);
     CAPE_LAUNCH_CHECK();
-    CAPE_LAUNCH(scan_search_kernel, dim3((unsigned)groups), dim3(SB), 0, st, (const float4 *)rec, x, ldx, points, ldp, count, V, F, M,
-                p.tiles, p.split, p.tiles_per_part, (long long)N * M, cand);
-    CAPE_LAUNCH_CHECK();
-    CAPE_LAUNCH(scan_finish_kernel, dim3(cape_grid_blocks((long long)N * M, LB, MAXB)), dim3(LB), 0, st, x, ldx, faces, points, ldp,
-                count, (const uint2 *)cand, p.split, N, V, M, face, bary, d2);
-    CAPE_LAUNCH_CHECK();
-    return CAPE_OK;
+    return forward(
+        groups, (long long)N * M,
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(scan_search_kernel, grid, block, 0, st, (const float4 *)rec, x, ldx, points, ldp, count, V, F, M, p.tiles,
+                        p.split, p.tiles_per_part, (long long)N * M, cand);
+        },
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(scan_finish_kernel, grid, block, 0, st, x, ldx, faces, points, ldp, count, (const uint2 *)cand, p.split, N,
+                        V, M, face, bary, d2);
+        });
 }
 
 extern "C" int cape_scan_nearest_bwd(const float *x, int32_t ldx, const int32_t *faces, const float *points, int32_t ldp,
@@ -386,10 +339,9 @@ extern "C" int cape_scan_nearest_bwd(const float *x, int32_t ldx, const int32_t 
                                      int64_t workspace_bytes, void *stream) {
     if (!x || !faces || !points || !face || !bary || !g || !dx || !workspace) return CAPE_EINVAL;
     if (!sizes_ok(N, V, F, M) || ldx < 3 || ldp < 3 || ldd < 3 || (dp && lddp < 3)) return CAPE_EINVAL;
-    if (((uintptr_t)workspace & 15) != 0 || workspace_bytes < bwd_bytes(N, M)) return CAPE_EINVAL;
     const int vtiles = (V + LB - 1) / LB;
     const long long groups = (long long)N * vtiles;
-    if (groups >= ((long long)1 << 31)) return CAPE_EINVAL;
+    if (!launch_ok(workspace, workspace_bytes, bwd_bytes(N, M), groups)) return CAPE_EINVAL;
     hipStream_t st = (hipStream_t)stream;
     int4 *ids = (int4 *)workspace;
     double *pay = (double *)((char *)workspace + (int64_t)N * M * 16);

@@ -41,6 +41,20 @@ def _trunc_normal(rng, shape, std=0.1):
     return (std * out).reshape(shape).astype(np.float32)
 
 
+class _Series(object):
+    """The per-sample series of a fit's batch: one zeroed [steps + 1, batch_size] device tensor per name (``name=dtype``); a
+    step writes its row (``series[name][step]``), ``numpy(nb)`` returns the valid columns [:, :nb] by name."""
+
+    def __init__(self, steps, batch_size, device, **dtypes):
+        self._rows = {k: torch.zeros((steps + 1, batch_size), dtype=dt, device=device) for k, dt in dtypes.items()}
+
+    def __getitem__(self, name):
+        return self._rows[name]
+
+    def numpy(self, nb):
+        return {k: t[:, :nb].cpu().numpy() for k, t in self._rows.items()}
+
+
 class base_model(object):
     """Reference lib/models.py:13-227: hyper-parameters, operator name binding, variables."""
 
@@ -1681,6 +1695,18 @@ class CAPE(base_model):
                                          body.V, self.device)
         return body, pose, transl, dressing, cond, cond2
 
+    def _fit_arguments(self, size, body, pose, transl, dress, cond, cond2, z0, steps, optimize_transl):
+        """What fit_posed and fit_scan share of their arguments: ``_posed_arguments`` (``transl`` zeros when it is a leaf and
+        None), the starting codes ``z0`` [size, nz] (zeros) and ``steps``."""
+        nz = int(self.nz)
+        if transl is None and optimize_transl:
+            transl = np.zeros((size, 3), np.float32)
+        _, pose, transl, dressing, cond, cond2 = self._posed_arguments(size, body, pose, transl, dress, cond, cond2)
+        z0 = np.zeros((size, nz), np.float32) if z0 is None else np.asarray(z0, dtype=np.float32)
+        if z0.shape != (size, nz):
+            raise ValueError("z0: [%d, %d] expected" % (size, nz))
+        return pose, transl, dressing, cond, cond2, z0, int(steps)
+
     def decode_posed(self, data, cond, cond2, pose, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None,
                      return_normals=False):
         """``decode`` followed by demos.py's posing step (:155-161 / :207-213 dress, :267-283 / :312-326 SMPL forward), on
@@ -1787,20 +1813,14 @@ class CAPE(base_model):
         from . import smpl as smpl_mod
         body = getattr(body_model, 'model', body_model)
         target = np.asarray(target, dtype=np.float32)
-        size, V, bs, nz = target.shape[0], body.V, self.batch_size, int(self.nz)
+        size, V, bs = target.shape[0], body.V, self.batch_size
         if target.shape != (size, V, 3):
             raise ValueError("target: [size, %d, 3] expected, got %s" % (V, target.shape))
-        if transl is None and optimize_transl:
-            transl = np.zeros((size, 3), np.float32)
-        _, pose, transl, dressing, cond, cond2 = self._posed_arguments(size, body, pose, transl,
-                                                                       (mean, std, clothing_idx, minimal_shape), cond, cond2)
-        z0 = np.zeros((size, nz), np.float32) if z0 is None else np.asarray(z0, dtype=np.float32)
-        if z0.shape != (size, nz):
-            raise ValueError("z0: [%d, %d] expected" % (size, nz))
+        pose, transl, dressing, cond, cond2, z0, steps = self._fit_arguments(
+            size, body, pose, transl, (mean, std, clothing_idx, minimal_shape), cond, cond2, z0, steps, optimize_transl)
         w = np.ones(V, np.float32) if weights is None else np.asarray(weights, dtype=np.float32).reshape(-1)
         if w.shape != (V,) or not float(w.sum()) > 0.0:
             raise ValueError("weights: [%d] with a positive sum expected" % V)
-        steps = int(steps)
         lambda_vnormal = float(lambda_vnormal)
         if not np.isfinite(lambda_vnormal) or lambda_vnormal < 0:
             raise ValueError("lambda_vnormal must be finite and >= 0, got %r" % (lambda_vnormal,))
@@ -1814,7 +1834,7 @@ class CAPE(base_model):
         def data_term(begin, end):
             nb = end - begin
             tgt = self._padded(target, begin, end)
-            loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
+            series = _Series(steps, bs, self.device, loss=torch.float32, **(dict(normal=torch.float32) if lambda_vnormal else {}))
             grad = torch.zeros((bs, V, 3), dtype=torch.float32, device=self.device)       # padded rows stay zero
             if lambda_vnormal:
                 # w_v n_v(target) / sum w in fp64 (the term's value is summed in fp64), padded rows zero; the term's
@@ -1823,15 +1843,14 @@ class CAPE(base_model):
                     tnw = body.vertex_normals(tgt).double() * (w_dev.double() * inv_wsum)[None, :, None]
                     tnw[nb:] = 0.0
                     g_normal = (-lambda_vnormal * tnw).float()
-                normal = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
 
             def term(step, posed, want_grad):
-                smpl_mod.weighted_l2(posed, tgt, w_dev, inv_wsum, nb, loss[step], grad if want_grad else None)
+                smpl_mod.weighted_l2(posed, tgt, w_dev, inv_wsum, nb, series['loss'][step], grad if want_grad else None)
                 roots, seeds = [posed], [grad]
                 if lambda_vnormal:
                     nrm = body.vertex_normals_diff(posed) if want_grad else body.vertex_normals(posed)
                     # sum_v w_v / sum w = 1: the term is 1 - sum_v w_v n_v . n_v(target) / sum w
-                    normal[step, :nb] = (1.0 - (nrm.detach().double() * tnw).sum((1, 2)))[:nb].float()
+                    series['normal'][step, :nb] = (1.0 - (nrm.detach().double() * tnw).sum((1, 2)))[:nb].float()
                 if lambda_edge and want_grad:
                     # the batch mean of the training loss's edge term, scaled back to a sum over the samples
                     e_total, _ = ops.ReconEdgeLossFn.apply(posed[:nb], tgt[:nb], no_ref, ed, vptr, vidx, 0.0,
@@ -1843,13 +1862,7 @@ class CAPE(base_model):
                     seeds.append(g_normal)
                 return roots, seeds
 
-            def results():
-                out = dict(loss=loss[:, :nb].cpu().numpy())
-                if lambda_vnormal:
-                    out['normal'] = normal[:, :nb].cpu().numpy()
-                return out
-
-            return term, results
+            return term, series
 
         return self._fit_leaves(size, body, dressing, z0, cond, cond2, pose, transl, steps, lr, lambda_z, optimize_pose,
                                 optimize_transl, data_term)
@@ -1859,9 +1872,9 @@ class CAPE(base_model):
         """fit_posed's and fit_scan's batch loop: Adam on the leaves ``z`` (and ``pose`` / ``transl``) of
         decoder -> ``dressing.diff`` -> ``body.forward_diff`` per padded batch, with the model's variables frozen and its
         gradient buckets out of reach, and a last evaluation of the returned leaves as ``decode_posed`` evaluates them.
-        ``data_term(begin, end)`` returns per batch (term, results): ``term(step, posed, want_grad)`` records the step's values
-        and returns the (roots, seeds) of the one backward call; ``results()`` the batch's per-sample arrays [steps + 1, nb] by
-        name.  Arguments as ``_posed_arguments`` returns them; the device pass is open."""
+        ``data_term(begin, end)`` returns per batch (term, series): ``term(step, posed, want_grad)`` records the step's values
+        in ``series`` (a ``_Series``: the batch's per-sample arrays [steps + 1, nb] by name) and returns the (roots, seeds) of
+        the one backward call.  Arguments as ``_posed_arguments`` returns them; the device pass is open."""
         bs, nz = self.batch_size, int(self.nz)
         res = dict(z=[], pose=[], transl=[], posed=[], clothed=[])
         # the model's variables are constants here: no gradient bucket to write into and, while the steps run, nothing that
@@ -1883,7 +1896,7 @@ class CAPE(base_model):
                 bt = None if transl is None else self._padded(transl, begin, end).requires_grad_(bool(optimize_transl))
                 leaves = [z] + ([bp] if optimize_pose else []) + ([bt] if optimize_transl else [])
                 opt = torch.optim.Adam(leaves, lr=float(lr))
-                term, results = data_term(begin, end)
+                term, series = data_term(begin, end)
 
                 def evaluate(step, want_grad):
                     with self.variable_scope('generator'):
@@ -1910,7 +1923,7 @@ class CAPE(base_model):
                 res['transl'].append(None if bt is None else bt.detach()[:nb].cpu().numpy())
                 res['posed'].append(posed[:nb].cpu().numpy())
                 res['clothed'].append(T[:nb].cpu().numpy())
-                for k, a in results().items():
+                for k, a in series.numpy(nb).items():
                     res.setdefault(k, []).append(a)
         finally:
             self._grad_views = grad_views
@@ -1966,7 +1979,7 @@ class CAPE(base_model):
                 raise ValueError("mesh_max_dist must be >= 0 or None, got %r" % (mesh_max_dist,))
         body = getattr(body_model, 'model', body_model)
         pts, count = pad_points(scan)
-        size, M, V, bs, nz = pts.shape[0], pts.shape[1], body.V, self.batch_size, int(self.nz)
+        size, M, V, bs = pts.shape[0], pts.shape[1], body.V, self.batch_size
         if count is None:
             count = np.full(size, M, np.int32)
         mw = np.ones(V, np.float32) if mesh_weights is None else np.asarray(mesh_weights, dtype=np.float32)
@@ -1976,14 +1989,8 @@ class CAPE(base_model):
             max_dist = float(max_dist)
             if not max_dist >= 0.0:
                 raise ValueError("max_dist must be >= 0 or None, got %r" % (max_dist,))
-        if transl is None and optimize_transl:
-            transl = np.zeros((size, 3), np.float32)
-        _, pose, transl, dressing, cond, cond2 = self._posed_arguments(size, body, pose, transl,
-                                                                       (mean, std, clothing_idx, minimal_shape), cond, cond2)
-        z0 = np.zeros((size, nz), np.float32) if z0 is None else np.asarray(z0, dtype=np.float32)
-        if z0.shape != (size, nz):
-            raise ValueError("z0: [%d, %d] expected" % (size, nz))
-        steps = int(steps)
+        pose, transl, dressing, cond, cond2, z0, steps = self._fit_arguments(
+            size, body, pose, transl, (mean, std, clothing_idx, minimal_shape), cond, cond2, z0, steps, optimize_transl)
         limit = float('inf') if max_dist is None else max_dist * max_dist
         mesh_limit = float('inf') if mesh_max_dist is None else mesh_max_dist * mesh_max_dist
         self._open_pass()
@@ -2001,19 +2008,16 @@ class CAPE(base_model):
             cnt_dev = counts[1]
             inv_m = (1.0 / torch.as_tensor(np.maximum(cnt, 1)).to(self.device).double())[:, None]
             valid = torch.arange(M, device=self.device)[None, :] < cnt_dev[:, None]
-            loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
-            inliers = torch.zeros((steps + 1, bs), dtype=torch.int32, device=self.device)
-            if lambda_mesh:
-                mesh_loss = torch.zeros((steps + 1, bs), dtype=torch.float32, device=self.device)
-                mesh_inliers = torch.zeros((steps + 1, bs), dtype=torch.int32, device=self.device)
+            series = _Series(steps, bs, self.device, loss=torch.float32, inliers=torch.int32,
+                             **(dict(mesh_loss=torch.float32, mesh_inliers=torch.int32) if lambda_mesh else {}))
 
             def term(step, posed, want_grad):
                 d2 = body.scan_distance_diff(posed, p, counts) if want_grad else body.scan_distance(posed, p, counts)[0]
                 d = d2.detach()
                 mask = valid & (d <= limit)                                               # a NaN distance is no inlier
                 md = mask.double()
-                loss[step] = ((d.double() * md).nan_to_num_(nan=0.0).sum(1, keepdim=True) * inv_m)[:, 0].float()
-                inliers[step] = mask.sum(1).int()
+                series['loss'][step] = ((d.double() * md).nan_to_num_(nan=0.0).sum(1, keepdim=True) * inv_m)[:, 0].float()
+                series['inliers'][step] = mask.sum(1).int()
                 roots, seeds = [d2], [(md * inv_m).float()]
                 if lambda_mesh:
                     # the same checked counts: a padded row has none, its vertices come back NaN and are dropped
@@ -2021,19 +2025,13 @@ class CAPE(base_model):
                     e = e2.detach()
                     near = e <= mesh_limit                                                # a NaN distance is no inlier
                     wm = near.double() * mw_dev
-                    mesh_loss[step] = ((e.double() * wm).nan_to_num_(nan=0.0).sum(1) * inv_mwsum).float()
-                    mesh_inliers[step] = (near & mw_pos).sum(1).int()
+                    series['mesh_loss'][step] = ((e.double() * wm).nan_to_num_(nan=0.0).sum(1) * inv_mwsum).float()
+                    series['mesh_inliers'][step] = (near & mw_pos).sum(1).int()
                     roots.append(e2)
                     seeds.append((wm * (lambda_mesh * inv_mwsum)).float())
                 return roots, seeds
 
-            def results():
-                out = dict(loss=loss[:, :nb].cpu().numpy(), inliers=inliers[:, :nb].cpu().numpy())
-                if lambda_mesh:
-                    out.update(mesh_loss=mesh_loss[:, :nb].cpu().numpy(), mesh_inliers=mesh_inliers[:, :nb].cpu().numpy())
-                return out
-
-            return term, results
+            return term, series
 
         return self._fit_leaves(size, body, dressing, z0, cond, cond2, pose, transl, steps, lr, lambda_z, optimize_pose,
                                 optimize_transl, data_term)

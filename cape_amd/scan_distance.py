@@ -20,27 +20,21 @@ import numpy as np
 import torch
 
 from . import _lib
-from .vertex_normals import _p, _rows, _stream, validate_faces
+from ._device import check_tensor, ptr as _p, resolve_device, rows, stream as _stream, workspace
+from .vertex_normals import validate_faces
 
 
-def _points(name, t, N, dev):
-    """(M, leading dimension) of a float32 tensor [N, M, 3] on ``dev``: contiguous, or the [:, :, :3] view of wider rows."""
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev:
-        raise ValueError("%s: must be a float32 tensor on %s" % (name, dev))
-    if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] != N or t.shape[1] < 1:
-        raise ValueError("%s: [%d, M, 3] with M >= 1 expected, got %s" % (name, N, tuple(t.shape)))
-    M, ld = int(t.shape[1]), t.stride(1)
-    if t.stride(2) != 1 or ld < 3 or (N > 1 and t.stride(0) != M * ld):            # one sample: its stride is never used
-        raise ValueError("%s: rows of at least 3 floats, unit stride inside a row, samples %d rows apart expected" % (name, M))
-    return M, ld
+def point_rows(name, t, N, dev):
+    """(M, leading dimension) of a float32 tensor [N, M, 3] on ``dev``, by the rules of ``_device.rows``."""
+    return rows(name, t, dev, N=N)[1:]
 
 
-def _count(count, N, M, dev):
+def check_count(count, N, M, dev):
     """(host int32 [N], device int32 [N]) of ``count``, or (None, None): integers in [0, M], one per sample.  Checked on the
-    host copy; a device tensor comes to the host for that (a loop checks once: ``ScanDistance.counts``)."""
+    host copy; a device tensor comes to the host for that (a loop checks once: ``NearestDistance.counts``)."""
     if count is None:
         return None, None
-    if isinstance(count, tuple):                               # ScanDistance.counts: checked and uploaded before
+    if isinstance(count, tuple):                               # NearestDistance.counts: checked and uploaded before
         return count
     host = count.detach().cpu().numpy() if torch.is_tensor(count) else np.asarray(count)
     if host.shape != (N,) or not np.issubdtype(host.dtype, np.integer):
@@ -51,6 +45,9 @@ def _count(count, N, M, dev):
     if torch.is_tensor(count) and count.device == dev and count.dtype == torch.int32 and count.is_contiguous():
         return host, count
     return host, torch.as_tensor(host).to(dev)
+
+
+_points, _count = point_rows, check_count                      # the names the host tests import
 
 
 def pad_points(points):
@@ -76,130 +73,79 @@ def pad_points(points):
     return np.ascontiguousarray(a), None
 
 
-class ScanDistance(object):
-    """Closest points on meshes with the triangles ``faces`` [F, 3] over ``num_verts`` vertices."""
+class NearestDistance(object):
+    """What the two directions of the nearest search share: the device and the tables on it, decided and
+    uploaded on first use; ``count``; the workspace; ``forward``'s refusal of gradients; ``diff``; the point half of ``np``.
+    A direction is a subclass: its names (``_module``, ``_samples``), its ``_workspace_bytes`` entry, its host ``_tables``, and
+    ``_sizes``, ``_forward``, ``backward``, ``_grads`` and ``_first_np`` -- what it checks, launches and returns."""
 
-    def __init__(self, faces, num_verts, device=None):
-        self.V = int(num_verts)
-        if self.V < 1:
-            raise ValueError("num_verts: %r" % (num_verts,))
-        self.faces = validate_faces(faces, self.V)
-        self.F = int(self.faces.shape[0])
+    _module = _samples = _workspace_bytes = None
+    _tables = ()
+
+    def __init__(self, device=None):
         self._device = device
         self._dev = None
 
     def _upload(self):
-        """(device, faces) with the triangles on the device, uploaded on first use."""
+        """(device, tables...) with the host ``_tables`` on the device, decided and uploaded on first use."""
         if self._dev is None:
             _lib.require_gpu()
-            dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
-            faces = torch.as_tensor(self.faces).to(dev)
-            self._dev = (faces.device, faces)
+            dev = resolve_device(self._device)
+            self._dev = (dev,) + tuple(torch.as_tensor(a).to(dev) for a in self._tables)
         return self._dev
 
     @property
     def device(self):
         return self._upload()[0]
 
-    def plan(self, N, M):
-        """(split, face tile, points per workgroup) the library chooses for N samples of M points: a function of the sizes."""
-        out = (C.c_int32 * 3)()
-        _lib.check(_lib.lib.cape_scan_distance_plan(N, self.F, M, out), "cape_scan_distance_plan")
-        return tuple(out)
-
     def counts(self, count, N, M):
         """``count`` checked and uploaded once, for calls in a loop: pass the result as their ``count``."""
-        return _count(count, N, M, self._upload()[0])
+        return check_count(count, N, M, self.device)
 
-    def _workspace(self, N, M, dev):
-        need = int(_lib.lib.cape_scan_distance_workspace_bytes(N, self.V, self.F, M))
-        if need < 0:
-            _lib.check(need, "cape_scan_distance_workspace_bytes")
-        return torch.empty((need + 15) // 16 * 2, dtype=torch.float64, device=dev), need
+    def _workspace(self, dev, *sizes):
+        return workspace(self._workspace_bytes(*sizes), dev, self._workspace_bytes.__name__)
 
-    def forward(self, verts, points, count=None, out=None):
-        """(d2 [N, M], face [N, M] int32, bary [N, M, 3]) for ``verts`` [N, V, 3] and ``points`` [N, M, 3] (float32 on the
-        tables' device; rows may be wider than 3 floats, the padding is never read).  ``count`` [N] integers in [0, M] (host or
-        device; checked on the host), None: every row is a point.  ``out``: (d2, face, bary) contiguous tensors to write into.
-        No gradient: inputs that require one are refused with a RuntimeError (use ``diff``)."""
+    def _points_grad(self, dp, want_dp, N, M, dev):
+        """(dp, its leading dimension) for the gradient to the points: allocated when wanted and not given; (None, 3) when not
+        wanted."""
+        if dp is None and not want_dp:
+            return None, 3
+        if dp is None:
+            dp = torch.empty((N, M, 3), dtype=torch.float32, device=dev)
+        m2, lddp = point_rows("dp", dp, N, dev)
+        if m2 != M:
+            raise ValueError("dp: %d points for %d" % (m2, M))
+        return dp, lddp
+
+    def forward(self, first, points, count=None, out=None):
+        """The distances and the selection of ``first`` (the subclass's vertices or queries) against ``points`` [N, M, 3]:
+        float32 on the device; rows may be wider than 3 floats, the padding is never read.  ``count`` [N] integers in [0, M]
+        (host or device; checked on the host), None: every row is a point.  ``out``: contiguous tensors to write into.  No
+        gradient: inputs that require one are refused with a RuntimeError (use ``diff``)."""
         self._upload()
-        for t in (verts, points):
+        for t in (first, points):
             if torch.is_tensor(t) and t.requires_grad and torch.is_grad_enabled():
-                raise RuntimeError("cape_amd.scan_distance: forward only, an input requires grad (use diff)")
-        return self._forward(verts, points, count, out)
+                raise RuntimeError("cape_amd.%s: forward only, an input requires grad (use diff)" % self._module)
+        return self._forward(first, points, count, out)
 
-    def _forward(self, verts, points, count, out):
-        dev, faces = self._upload()
-        ldx = _rows("verts", verts, self.V, dev)
-        N = verts.shape[0]
-        M, ldp = _points("points", points, N, dev)
-        _, cnt = _count(count, N, M, dev)
-        if out is None:
-            out = (torch.empty((N, M), dtype=torch.float32, device=dev), torch.empty((N, M), dtype=torch.int32, device=dev),
-                   torch.empty((N, M, 3), dtype=torch.float32, device=dev))
-        d2, face, bary = out
-        for name, t, shape, dt in (("d2", d2, (N, M), torch.float32), ("face", face, (N, M), torch.int32),
-                                   ("bary", bary, (N, M, 3), torch.float32)):
-            if not torch.is_tensor(t) or t.dtype != dt or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("out %s: a contiguous %s tensor %s on %s expected" % (name, dt, shape, dev))
-        ws, need = self._workspace(N, M, dev)
-        _lib.check(_lib.lib.cape_scan_nearest_fwd(_p(verts), ldx, _p(faces), _p(points), ldp, None if cnt is None else _p(cnt), N,
-                                                  self.V, self.F, M, _p(face), _p(bary), _p(d2), _p(ws), need, _stream()),
-                   "cape_scan_nearest_fwd")
-        return d2, face, bary
-
-    def backward(self, verts, points, face, bary, g, want_dp=True, dx=None, dp=None):
-        """(dx [N, V, 3], dp [N, M, 3] or None) for the seed ``g`` [N, M] = dL/dd2 and a forward's ``face`` / ``bary``.  ``dx``
-        is overwritten.  ``dx`` / ``dp``: where to write (rows may be wider than 3 floats, the padding is never written)."""
-        dev, faces = self._upload()
-        ldx = _rows("verts", verts, self.V, dev)
-        N = verts.shape[0]
-        M, ldp = _points("points", points, N, dev)
-        g = g.to(device=dev, dtype=torch.float32).contiguous()
-        for name, t, shape, dt in (("face", face, (N, M), torch.int32), ("bary", bary, (N, M, 3), torch.float32),
-                                   ("gradient", g, (N, M), torch.float32)):
-            if t.dtype != dt or t.device != dev or tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError("%s: a contiguous %s tensor %s on %s expected" % (name, dt, shape, dev))
-        if dx is None:
-            dx = torch.empty((N, self.V, 3), dtype=torch.float32, device=dev)
-        ldd = _rows("dx", dx, self.V, dev)
-        if dx.shape[0] != N:
-            raise ValueError("dx: %d samples for %d" % (dx.shape[0], N))
-        lddp = 3
-        if want_dp or dp is not None:
-            if dp is None:
-                dp = torch.empty((N, M, 3), dtype=torch.float32, device=dev)
-            m2, lddp = _points("dp", dp, N, dev)
-            if m2 != M:
-                raise ValueError("dp: %d points for %d" % (m2, M))
-        ws, need = self._workspace(N, M, dev)
-        _lib.check(_lib.lib.cape_scan_nearest_bwd(_p(verts), ldx, _p(faces), _p(points), ldp, _p(face), _p(bary), _p(g), N, self.V,
-                                                  self.F, M, _p(dx), ldd, None if dp is None else _p(dp), lddp, _p(ws), need,
-                                                  _stream()), "cape_scan_nearest_bwd")
-        return dx, dp
-
-    def diff(self, verts, points, count=None, return_selection=False):
-        """``forward``'s d2 (bitwise the same values) as an autograd function: a gradient on it flows to ``verts`` and to
-        ``points`` where they require one.  The chosen faces and barycentrics are saved, not recomputed, and are constants of
-        the backward (``return_selection``: (d2, face, bary) instead of d2); fixed-order sums, the same inputs give the same
-        bits."""
-        dev = self._upload()[0]
-        _rows("verts", verts, self.V, dev)
-        _points("points", points, verts.shape[0], dev)
-        res = _ScanDistanceFn.apply(self, verts, points, count)
+    def diff(self, first, points, count=None, return_selection=False):
+        """``forward``'s d2 (bitwise the same values) as an autograd function: a gradient on it flows to ``first`` and to
+        ``points`` where they require one (points that require none cost nothing).  The selection is saved, not recomputed,
+        and is a constant of the backward (``return_selection``: all of ``forward``'s tensors instead of d2); fixed-order
+        sums, the same inputs give the same bits."""
+        self._sizes(first, points, self.device)
+        res = _NearestFn.apply(self, first, points, count)
         return res if return_selection else res[0]
 
-    def np(self, verts, points):
-        """``forward``, numpy in, numpy out: ``verts`` [N, V, 3] or [V, 3]; ``points`` [N, M, 3], [M, 3] for one mesh, or a
-        list of N arrays [m_n, 3] (padded to the longest; the padding comes back as face -1, d2 0, bary 0).  Returns
-        (d2 [N, M] float32, face [N, M] int32, bary [N, M, 3] float32)."""
-        v = np.asarray(verts, dtype=np.float32)
-        x = np.ascontiguousarray(v.reshape(-1, self.V, 3))
+    def np(self, first, points):
+        """``forward``, numpy in, numpy out: ``points`` [N, M, 3], [M, 3] for one sample, or a list of N arrays [m_n, 3]
+        (padded to the longest)."""
+        x = self._first_np(first)
         if not isinstance(points, (list, tuple)) and np.asarray(points).ndim == 2:
             points = np.asarray(points)[None]
         pts, count = pad_points(points)
         if pts.shape[0] != x.shape[0]:
-            raise ValueError("points: %d samples for %d meshes" % (pts.shape[0], x.shape[0]))
+            raise ValueError("points: %d samples for %d %s" % (pts.shape[0], x.shape[0], self._samples))
         dev = self.device
         with torch.no_grad():
             out = self.forward(torch.as_tensor(x).to(dev), torch.as_tensor(pts).to(dev), count)
@@ -208,21 +154,96 @@ class ScanDistance(object):
     __call__ = forward
 
 
-class _ScanDistanceFn(torch.autograd.Function):
+class _NearestFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, sd, verts, points, count):
-        ctx.sd = sd
-        d2, face, bary = sd._forward(verts.detach(), points.detach(), count, None)
-        ctx.save_for_backward(verts, points, face, bary)
+    def forward(ctx, owner, first, points, count):
+        ctx.owner = owner
+        # checked once: the backward passes the pair on (``diff`` has checked the shapes)
+        count = check_count(count, first.shape[0], points.shape[1], owner.device)
+        ctx.count = None if count[0] is None else count
+        res = owner._forward(first.detach(), points.detach(), ctx.count, None)
+        ctx.save_for_backward(first, points, *res[1:])
         ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(face, bary)
-        return d2, face, bary
+        ctx.mark_non_differentiable(*res[1:])
+        return res
 
     @staticmethod
-    def backward(ctx, g, _gface=None, _gbary=None):
+    def backward(ctx, g, *_):
         if g is None or not (ctx.needs_input_grad[1] or ctx.needs_input_grad[2]):
             return None, None, None, None
-        verts, points, face, bary = ctx.saved_tensors
+        first, points, *selection = ctx.saved_tensors
         with torch.no_grad():
-            dx, dp = ctx.sd.backward(verts.detach(), points.detach(), face, bary, g, want_dp=ctx.needs_input_grad[2])
-        return None, dx if ctx.needs_input_grad[1] else None, dp, None
+            d_first, d_points = ctx.owner._grads(first.detach(), points.detach(), selection, g, ctx.count, ctx.needs_input_grad[2])
+        return None, d_first if ctx.needs_input_grad[1] else None, d_points, None
+
+
+class ScanDistance(NearestDistance):
+    """Closest points on meshes with the triangles ``faces`` [F, 3] over ``num_verts`` vertices.  ``forward(verts, points)``:
+    (d2 [N, M], face [N, M] int32, bary [N, M, 3]) for ``verts`` [N, V, 3]; ``np`` takes ``verts`` [N, V, 3] or [V, 3] and
+    returns the padding as face -1, d2 0, bary 0."""
+
+    _module, _samples, _workspace_bytes = "scan_distance", "meshes", _lib.lib.cape_scan_distance_workspace_bytes
+
+    def __init__(self, faces, num_verts, device=None):
+        NearestDistance.__init__(self, device)
+        self.V = int(num_verts)
+        if self.V < 1:
+            raise ValueError("num_verts: %r" % (num_verts,))
+        self.faces = validate_faces(faces, self.V)
+        self.F = int(self.faces.shape[0])
+        self._tables = (self.faces,)
+
+    def plan(self, N, M):
+        """(split, face tile, points per workgroup) the library chooses for N samples of M points: a function of the sizes."""
+        out = (C.c_int32 * 3)()
+        _lib.check(_lib.lib.cape_scan_distance_plan(N, self.F, M, out), "cape_scan_distance_plan")
+        return tuple(out)
+
+    def _sizes(self, verts, points, dev):
+        """(N, V, M, leading dimensions of ``verts`` and ``points``), checked."""
+        N, V, ldx = rows("verts", verts, dev, R=self.V)
+        _, M, ldp = rows("points", points, dev, N=N)
+        return N, V, M, ldx, ldp
+
+    def _forward(self, verts, points, count, out):
+        dev, faces = self._upload()
+        N, V, M, ldx, ldp = self._sizes(verts, points, dev)
+        _, cnt = check_count(count, N, M, dev)
+        if out is None:
+            out = (torch.empty((N, M), dtype=torch.float32, device=dev), torch.empty((N, M), dtype=torch.int32, device=dev),
+                   torch.empty((N, M, 3), dtype=torch.float32, device=dev))
+        d2, face, bary = out
+        check_tensor("out d2", d2, torch.float32, (N, M), dev)
+        check_tensor("out face", face, torch.int32, (N, M), dev)
+        check_tensor("out bary", bary, torch.float32, (N, M, 3), dev)
+        ws, need = self._workspace(dev, N, V, self.F, M)
+        _lib.check(_lib.lib.cape_scan_nearest_fwd(_p(verts), ldx, _p(faces), _p(points), ldp, _p(cnt), N, V, self.F, M, _p(face),
+                                                  _p(bary), _p(d2), _p(ws), need, _stream()), "cape_scan_nearest_fwd")
+        return d2, face, bary
+
+    def backward(self, verts, points, face, bary, g, want_dp=True, dx=None, dp=None):
+        """(dx [N, V, 3], dp [N, M, 3] or None) for the seed ``g`` [N, M] = dL/dd2 and a forward's ``face`` / ``bary``.  ``dx``
+        is overwritten.  ``dx`` / ``dp``: where to write (rows may be wider than 3 floats, the padding is never written)."""
+        dev, faces = self._upload()
+        N, V, M, ldx, ldp = self._sizes(verts, points, dev)
+        g = g.to(device=dev, dtype=torch.float32).contiguous()
+        check_tensor("face", face, torch.int32, (N, M), dev)
+        check_tensor("bary", bary, torch.float32, (N, M, 3), dev)
+        check_tensor("gradient", g, torch.float32, (N, M), dev)
+        if dx is None:
+            dx = torch.empty((N, V, 3), dtype=torch.float32, device=dev)
+        n2, _, ldd = rows("dx", dx, dev, R=V)
+        if n2 != N:
+            raise ValueError("dx: %d samples for %d" % (n2, N))
+        dp, lddp = self._points_grad(dp, want_dp, N, M, dev)
+        ws, need = self._workspace(dev, N, V, self.F, M)
+        _lib.check(_lib.lib.cape_scan_nearest_bwd(_p(verts), ldx, _p(faces), _p(points), ldp, _p(face), _p(bary), _p(g), N, V,
+                                                  self.F, M, _p(dx), ldd, _p(dp), lddp, _p(ws), need, _stream()),
+                   "cape_scan_nearest_bwd")
+        return dx, dp
+
+    def _grads(self, verts, points, selection, g, count, want_dp):
+        return self.backward(verts, points, selection[0], selection[1], g, want_dp=want_dp)
+
+    def _first_np(self, verts):
+        return np.ascontiguousarray(np.asarray(verts, dtype=np.float32).reshape(-1, self.V, 3))

@@ -35,16 +35,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._device import ptr as _p, resolve_device, stream as _stream
 
 MAX_JOINTS = 64
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 # ---- model files ----------------------------------------------------------------------------------------------------------
@@ -164,7 +157,7 @@ class SMPL(object):
         """The device arrays, uploaded on first use (a model can be read and inspected without a GPU)."""
         if self._dev is None:
             _lib.require_gpu()
-            dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
+            dev = resolve_device(self._device)
             self._dev = types.SimpleNamespace(device=dev, **{k: torch.as_tensor(np.ascontiguousarray(a, dtype=dt)).to(dev)
                                                              for k, (a, dt) in self.layouts.items()})
         return self._dev

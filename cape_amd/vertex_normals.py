@@ -10,21 +10,12 @@ The normal of a vertex is the normalised sum of the UNIT normals of its faces --
 reference have it.  Area weighting is the one-line variant that sums the unnormalised cross products instead; it is not
 implemented.  A degenerate face adds nothing, a vertex without faces gets a zero normal.  There is no CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _lib
+from ._device import ptr as _p, resolve_device, rows, stream as _stream
 from .graph import vertex_face_table
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return C.c_void_p(t.data_ptr())
 
 
 def validate_faces(faces, num_verts):
@@ -43,17 +34,8 @@ def validate_faces(faces, num_verts):
 
 
 def _rows(name, t, V, dev):
-    """(leading dimension) of a float32 tensor [N, V, 3] on the device ``dev`` whose rows are ld >= 3 floats apart and whose
-    samples are V rows apart: a contiguous tensor, or the [:, :, :3] view of one with wider rows.  Anything else -- a host
-    tensor, one on another device than the tables -- is a ValueError: the kernels would read through its pointer."""
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != dev:
-        raise ValueError("%s: must be a float32 tensor on %s" % (name, dev))
-    if t.dim() != 3 or tuple(t.shape[1:]) != (V, 3) or t.shape[0] < 1:
-        raise ValueError("%s: [N, %d, 3] expected, got %s" % (name, V, tuple(t.shape)))
-    ld = t.stride(1)
-    if t.stride(2) != 1 or ld < 3 or t.stride(0) != V * ld:
-        raise ValueError("%s: rows of at least 3 floats, unit stride inside a row, samples %d rows apart expected" % (name, V))
-    return ld
+    """The leading dimension of a float32 tensor [N, V, 3] on ``dev``, by the rules of ``_device.rows``."""
+    return rows(name, t, dev, R=V)[2]
 
 
 class VertexNormals(object):
@@ -73,9 +55,8 @@ class VertexNormals(object):
         """(device, faces, vptr, vidx) with the tables on the device, uploaded on first use."""
         if self._dev is None:
             _lib.require_gpu()
-            dev = torch.device(self._device) if self._device is not None else torch.device("cuda", torch.cuda.current_device())
-            tables = tuple(torch.as_tensor(a).to(dev) for a in (self.faces, self.vptr, self.vidx))
-            self._dev = (tables[0].device,) + tables          # the device as tensors report it ("cuda" -> "cuda:0")
+            dev = resolve_device(self._device)
+            self._dev = (dev,) + tuple(torch.as_tensor(a).to(dev) for a in (self.faces, self.vptr, self.vidx))
         return self._dev
 
     @property

@@ -552,8 +552,8 @@ __global__ __launch_bounds__(256) void dw_reduce_batch_kernel(DwReduceBatch B) {
 }
 
 // es = bytes per activation element (4: fp32, 2: bf16 storage)
-inline int fill_src(SrcDev &d, const cape_src_t &s, int es = 4) {
-    if (!s.x || s.C <= 0 || s.ldx < s.C) return CAPE_EINVAL;
+inline bool src_ok(const cape_src_t &s) { return s.x && s.C > 0 && s.ldx >= s.C; }
+inline void set_src(SrcDev &d, const cape_src_t &s, int es = 4) {
     d.x = s.x; d.xs = s.x_sample_stride; d.ldx = s.ldx; d.C = s.C;
     d.w = s.w; d.wrs = s.w_rs; d.wcs = s.w_cs;
     d.w2 = s.w2; d.w2rs = s.w2_rs; d.w2cs = s.w2_cs;
@@ -562,6 +562,10 @@ inline int fill_src(SrcDev &d, const cape_src_t &s, int es = 4) {
     d.wp = d.wp2 = 0;
     d.rm = nullptr;
     d.rmw = 0;
+}
+inline int fill_src(SrcDev &d, const cape_src_t &s, int es = 4) {
+    if (!src_ok(s)) return CAPE_EINVAL;
+    set_src(d, s, es);
     return CAPE_OK;
 }
 
@@ -694,46 +698,57 @@ inline void fill_h2_dw(DwParams &p, const cape_h2_dw_t *h2) {
     p.dz2rm = h2->dz2_rowmax; p.dz2rmw = h2->dz2_rowmax_w;
 }
 
-// Kernel choice of one weight-gradient launch (pure function of the arguments): 0 = generic form (gconv_dw_kernel),
-// 1 = pipelined plain kernel on the exact-fp32 MFMA (dw_plain_kernel), 2 = packed narrow sources (dw_packed_kernel),
-// 3 = plain sources on the bf16 pipe with the exact three-way operand split (dw_split_kernel).  Fills the tile plan.
-inline int choose_dw(const cape_src_t *srcs, int nsrc, const float *dz, int64_t dz_sample_stride, int32_t lddz,
-                     const float *dz2, uint32_t dz2_mask, int N, int Mo, int F, DwPlan &pl, bool bf16 = false) {
+// One weight-gradient call as every extern "C" entry point receives it.  dz / dz2 are float or, with bf16, cape_bf16 storage
+// (strides in elements); h2: row bounds of the operands or null; the plan queries leave accumulate and the workspace empty.
+struct DwCall {
+    const cape_src_t *srcs;
+    int nsrc, N, Mo, F, accumulate;
+    const float *dz, *dz2;
+    int64_t dz_sample_stride;
+    int32_t lddz;
+    uint32_t dz2_mask;
+    void *workspace;
+    int64_t workspace_bytes;
+    bool bf16;
+    const cape_h2_dw_t *h2;
+};
+
+// Kernel family of one weight-gradient launch (pure function of the arguments): DW_GENERIC, DW_PLAIN, DW_PACKED (narrow
+// sources sharing a tile) or DW_SPLIT (plain sources on the bf16 pipe).  Fills the tile plan.
+inline int choose_dw(const DwCall &c, DwPlan &pl) {
     static const int dwp_on = getenv("CAPE_DW_PLAIN") ? atoi(getenv("CAPE_DW_PLAIN")) : 1;      // 0: A/B against the generic kernel
-    const int es = bf16 ? 2 : 4;
-    const bool dzvec = dw_dz_vec(dz, dz_sample_stride, lddz, dz2, es);
-    const bool plain = dwp_on && dzvec && (((F + 3) & ~3) <= lddz) && dw_srcs_plain(srcs, nsrc, es);
-    if (bf16) {
+    const cape_src_t *srcs = c.srcs;
+    const int nsrc = c.nsrc, N = c.N, Mo = c.Mo, F = c.F, es = c.bf16 ? 2 : 4;
+    const bool two = c.dz2 && c.dz2_mask;
+    const bool dzvec = dw_dz_vec(c.dz, c.dz_sample_stride, c.lddz, c.dz2, es);
+    const bool plain = dwp_on && dzvec && (((F + 3) & ~3) <= c.lddz) && dw_srcs_plain(srcs, nsrc, es);
+    int sumC = 0;
+    bool c4 = true;
+    for (int i = 0; i < nsrc; ++i) { c4 = c4 && (srcs[i].C & 3) == 0; sumC += srcs[i].C; }
+    // packing pays where several sources fit ONE tile (narrow layers of the fine mesh levels)
+    // (and the output is narrow: with F > 64 the single packed tile over-splits the rows -- measured 1.8x slower)
+    const bool packs = plain && c4 && !two && nsrc > 1 && sumC <= 128 && F <= 64;
+    if (c.bf16) {
         // bf16 storage: the split-pipe kernel with one plane where it applies (plain sources, whole float4-equivalent
         // columns, even F); the 3-channel ends take the pipelined fp32-MFMA kernels like the fp32 path (packed when
         // several narrow sources share a tile, plain otherwise); the generic kernel for everything else
-        bool c4b = true;
-        int sumCb = 0;
-        for (int i = 0; i < nsrc; ++i) { c4b = c4b && (srcs[i].C & 3) == 0; sumCb += srcs[i].C; }
-        if (plain && c4b && (F & 1) == 0) {
+        if (plain && c4 && (F & 1) == 0) {
             plan_dw(srcs, nsrc, N, Mo, F, pl);
-            return 3;
+            return DW_SPLIT;
         }
-        if (plain && c4b && !(dz2 && dz2_mask) && nsrc > 1 && sumCb <= 128 && F <= 64) {
+        if (packs) {
             plan_dw_plain(srcs, nsrc, N, Mo, F, true, pl);
-            return 2;
+            return DW_PACKED;
         }
         plan_dw(srcs, nsrc, N, Mo, F, pl);
-        return plain ? 1 : 0;
+        return plain ? DW_PLAIN : DW_GENERIC;
     }
-    int sumC = 0;
-    for (int i = 0; i < nsrc; ++i) sumC += srcs[i].C;
-    // packing pays where several sources fit ONE tile (narrow layers of the fine mesh levels)
-    // (and the output is narrow: with F > 64 the single packed tile over-splits the rows -- measured 1.8x slower)
-    bool c4 = true;
-    for (int i = 0; i < nsrc; ++i) c4 = c4 && (srcs[i].C & 3) == 0;
-    const bool packed = plain && c4 && !(dz2 && dz2_mask) && nsrc > 1 && sumC <= 128 && F <= 64;
     // un-packed plain launches run on the bf16 pipe (dw_split_kernel); CAPE_DW_BF16X6=0 keeps them on the fp32 MFMA
     static const int dws_on = getenv("CAPE_DW_BF16X6") ? atoi(getenv("CAPE_DW_BF16X6")) : CAPE_DW_BF16X6_DEFAULT;
-    const bool dw_split = dws_on && plain && !packed && c4 && (F & 1) == 0;
-    if (packed) plan_dw_plain(srcs, nsrc, N, Mo, F, true, pl);
+    const bool dw_split = dws_on && plain && !packs && c4 && (F & 1) == 0;
+    if (packs) plan_dw_plain(srcs, nsrc, N, Mo, F, true, pl);
     else plan_dw(srcs, nsrc, N, Mo, F, pl);
-    return packed ? 2 : dw_split ? 3 : plain ? 1 : 0;
+    return packs ? DW_PACKED : dw_split ? DW_SPLIT : plain ? DW_PLAIN : DW_GENERIC;
 }
 
 // Kernel choice of one forward launch (pure function of the arguments).
@@ -923,6 +938,163 @@ int gconv_fwd_impl(const cape_src_t *srcs, int32_t nsrc, float *y, int64_t y_sam
     return CAPE_OK;
 }
 
+// =============================================================================================================
+// Weight gradient, host side.  Every entry point turns its arguments into a DwCall; dw_resolve decides ONCE what that call runs
+// (kernel, tiles and splits, kernel arguments, grid, workspace need, the slab reduction) and every consumer reads the resulting
+// DwLaunch: the plan queries copy four integers out of it, the stages hand it to dw_contract and / or dw_reduce, the batched
+// reduction and contraction collect their items'.  A new kernel registers as a DwKernelId, in dw_resolve and in dw_contract.
+// =============================================================================================================
+inline long long dw_workspace_need(const DwPlan &pl) { return pl.slab * pl.ngroups * pl.rsplit * (long long)sizeof(float); }
+
+struct DwLaunch {
+    int kernel;                        // DwKernelId
+    bool bf16, v4;                     // storage type of the operands; DW_H2 only: the 16-byte-load instantiation
+    DwPlan pl;                         // (DW_H2: split for DW_SLOTS_PIPELINED)
+    DwParams p;
+    unsigned grid;
+    DwReduceParams rp;                 // the fixed-order slab reduction: its arguments, float4 form or not, blocks of 256 threads
+    bool rvec;
+    int rblocks;
+};
+
+// launchable = false (the plan queries): nothing is checked that only a launch needs -- the workspace, dz2 behind its mask, the
+// sources' pointers and pitches -- and L describes the launch those arguments would get.
+int dw_resolve(const DwCall &c, DwLaunch &L, bool launchable = true) {
+    if (!c.srcs || c.nsrc < 1 || c.nsrc > CAPE_MAX_SRC || !c.dz || c.N < 1 || c.Mo < 1 || c.F < 1 || c.lddz < c.F) return CAPE_EINVAL;
+    if (launchable && (!c.workspace || (c.dz2_mask && !c.dz2))) return CAPE_EINVAL;
+    const int nsrc = c.nsrc, es = c.bf16 ? 2 : 4;
+    DwPlan &pl = L.pl;
+    DwParams &p = L.p;
+    DwReduceParams &rp = L.rp;
+    const int fam = choose_dw(c, pl);
+    // the operands
+    p.nsrc = nsrc;
+    for (int i = 0; i < nsrc; ++i) set_src(p.s[i], c.srcs[i], es);
+    p.dz = c.dz; p.dz2 = c.dz2; p.dz2_mask = c.dz2 ? c.dz2_mask : 0u; p.dzs = c.dz_sample_stride; p.lddz = c.lddz;
+    p.dzvec = dw_dz_vec(c.dz, c.dz_sample_stride, c.lddz, c.dz2, es);
+    p.N = c.N; p.Mo = c.Mo; p.F = c.F;
+    fill_h2_dw(p, c.bf16 ? nullptr : c.h2);
+    // the kernel: a narrow form where one applies, else the two-piece kernel for a DW_SPLIT launch whose operands all carry row
+    // bounds.  One workgroup per CU (256 slots) for that pipelined kernel ONLY: the narrow kernels are serial ones and keep the
+    // 512-slot plan whether or not the launch carries row bounds.
+    L.bf16 = c.bf16;
+    L.kernel = fam;
+    if (const int narrow = dw_narrow_mode(p, fam, c.bf16)) {
+        L.kernel = narrow;                                        // narrow.h: same splits and slabs, tile 0's workgroups do all sources
+    } else if (fam == DW_SPLIT && h2_dw_eligible(p)) {
+        L.kernel = DW_H2;                                         // fp16 two-piece operands: same tiles and slabs, fewer splits
+        plan_dw_splits(c.N, c.Mo, pl, DW_SLOTS_PIPELINED);
+    }
+    L.v4 = L.kernel == DW_H2 && h2_dw_v4(p, pl.ct, pl.ft);
+    // tiles, splits and slabs
+    const bool packed = fam == DW_PACKED;
+    int toff = 0;
+    long long poff = 0;
+    for (int i = 0; i <= nsrc; ++i) {
+        p.tile_off[i] = toff; p.part_off[i] = rp.part_off[i] = poff;
+        p.vstart[i] = packed ? pl.vstart[i] : 0;
+        if (i == nsrc) break;
+        toff += packed ? 0 : pl.ctiles[i] * pl.ftiles;
+        poff += (long long)c.srcs[i].C * c.F;
+    }
+    p.ftiles = pl.ftiles;
+    p.rsplit = pl.rsplit; p.rows_per_split = pl.rows_per_split;
+    p.ngroups = pl.ngroups; p.samples_per_group = pl.samples_per_group;
+    p.ws = (float *)c.workspace; p.slab = pl.slab;
+    L.grid = (unsigned)(pl.ntiles * ((pl.ngroups * pl.rsplit + 7) / 8) * 8);                  // cape_map_dw_block
+    if (launchable) {
+        if (c.workspace_bytes < dw_workspace_need(pl)) return CAPE_EWORKSPACE;
+        for (int i = 0; i < nsrc; ++i)
+            if (!c.srcs[i].w || !src_ok(c.srcs[i])) return CAPE_EINVAL;
+    }
+    // the slab reduction.  The float4 form sums a quad's splits serially: only when the slab alone fills the chip (>= 256 blocks
+    // of quads); small slabs with many splits (fine mesh levels) take the kernel that also spreads the splits over 16 lanes
+    rp.nsrc = nsrc; rp.F = c.F; rp.nsplit = pl.ngroups * pl.rsplit; rp.accumulate = c.accumulate;
+    rp.ws = (const float *)c.workspace; rp.slab = pl.slab;
+    L.rvec = (c.F & 3) == 0 && (pl.slab & 3) == 0 && (reinterpret_cast<uintptr_t>(c.workspace) & 15) == 0 && poff >= 262144;
+    for (int i = 0; i < nsrc; ++i) {
+        const cape_src_t &s = c.srcs[i];
+        rp.w[i] = const_cast<float *>(s.w); rp.wrs[i] = s.w_rs; rp.wcs[i] = s.w_cs;
+        L.rvec = L.rvec && s.w_cs == 1 && (s.w_rs & 3) == 0 && (reinterpret_cast<uintptr_t>(s.w) & 15) == 0;
+    }
+    L.rblocks = L.rvec ? (int)((poff / 4 + 255) / 256) : (int)((poff + 15) / 16);
+    return CAPE_OK;
+}
+
+// The tile kernels (DW_GENERIC .. DW_SPLIT) for storage type AT: ONE ladder over the four square tiles; only dw_packed has a 32-wide one
+using DwKernelFn = void (*)(DwParams);
+template <typename AT>
+DwKernelFn dw_tile_kernel(int kernel, int ct, int ft) {
+#define DW_TILES(K, ...)                                                                                                    \
+    (ct == 64 && ft == 64 ? DwKernelFn(K<64, 64, __VA_ARGS__>) : ct == 64 ? DwKernelFn(K<64, 128, __VA_ARGS__>)              \
+     : ft == 64           ? DwKernelFn(K<128, 64, __VA_ARGS__>) : DwKernelFn(K<128, 128, __VA_ARGS__>))
+    switch (kernel) {
+    case DW_PACKED: return ft == 32 ? DwKernelFn(dw_packed_kernel<128, 32, 4, 1, AT>) : DW_TILES(dw_packed_kernel, 2, 2, AT);
+    case DW_SPLIT: return DW_TILES(dw_split_kernel, AT);
+    case DW_PLAIN: return DW_TILES(dw_plain_kernel, 2, 2, AT);
+    default: return DW_TILES(gconv_dw_kernel, AT);
+    }
+#undef DW_TILES
+}
+
+// the contraction: partial slabs into the workspace
+int dw_contract(const DwLaunch &L, hipStream_t st) {
+    const DwParams &p = L.p;
+    const dim3 grid(L.grid), block(256);
+    if (L.kernel == DW_NARROW_IN) {
+        CAPE_LAUNCH(dw_narrow_in_kernel, grid, block, 32768, st, p, narrow_lpr(p.F / 4), L.pl.ntiles);
+    } else if (L.kernel == DW_NARROW_OUT) {
+        const int sumC = (int)(p.part_off[p.nsrc] / p.F);
+        CAPE_LAUNCH(dw_narrow_out_kernel, grid, block, 16384, st, p, narrow_lpr(sumC / 4), L.pl.ntiles);
+    } else if (L.kernel == DW_H2) {
+        h2_dw_launch(p, L.pl.ct, L.pl.ft, L.v4, grid, st);
+    } else {
+        const DwKernelFn k = L.bf16 ? dw_tile_kernel<cape_bf16>(L.kernel, L.pl.ct, L.pl.ft) : dw_tile_kernel<float>(L.kernel, L.pl.ct, L.pl.ft);
+        CAPE_LAUNCH(k, grid, block, 0, st, p);
+    }
+    CAPE_LAUNCH_CHECK();
+    return CAPE_OK;
+}
+
+// the reduction: the slabs of an earlier dw_contract of the same launch, summed in a fixed order into the gradient blocks
+int dw_reduce(const DwLaunch &L, hipStream_t st) {
+    if (L.rvec) CAPE_LAUNCH(dw_reduce_vec_kernel, dim3((unsigned)L.rblocks), dim3(256), 0, st, L.rp);
+    else CAPE_LAUNCH(dw_reduce_kernel, dim3((unsigned)L.rblocks), dim3(256), 0, st, L.rp);
+    CAPE_LAUNCH_CHECK();
+    return CAPE_OK;
+}
+
+// the arguments of an entry point / an item of a batch as a DwCall (the bf16 entry points' void * become float * here)
+inline DwCall dw_call(const cape_src_t *srcs, int32_t nsrc, const void *dz, int64_t dz_sample_stride, int32_t lddz, const void *dz2,
+                      uint32_t dz2_mask, int32_t N, int32_t Mo, int32_t F, bool bf16, const cape_h2_dw_t *h2 = nullptr,
+                      int32_t accumulate = 0, void *workspace = nullptr, int64_t workspace_bytes = 0) {
+    return DwCall{srcs, nsrc, N, Mo, F, accumulate, (const float *)dz, (const float *)dz2, dz_sample_stride, lddz, dz2_mask,
+                  workspace, workspace_bytes, bf16, h2};
+}
+inline DwCall dw_call(const cape_dw_item_t &t) {
+    return dw_call(t.srcs, t.nsrc, t.dz, t.dz_sample_stride, t.lddz, t.dz2, t.dz2_mask, t.N, t.Mo, t.F, t.bf16 != 0, t.h2, t.accumulate,
+                   t.workspace, t.workspace_bytes);
+}
+
+// plan[0..3] = kernel id, tile rows (channels), tile columns, partial slabs
+int dw_plan_query(const DwCall &c, int32_t plan[4]) {
+    if (!plan) return CAPE_EINVAL;
+    DwLaunch L;
+    const int rc = dw_resolve(c, L, false);
+    if (rc) return rc;
+    plan[0] = L.kernel; plan[1] = L.pl.ct; plan[2] = L.pl.ft; plan[3] = L.pl.ngroups * L.pl.rsplit;
+    return CAPE_OK;
+}
+
+// stage 0: contraction and reduction, 1: contraction only, 2: reduction only (of an earlier stage-1 call with the same arguments)
+int dw_run(const DwCall &c, int stage, void *stream) {
+    if (stage < 0 || stage > 2) return CAPE_EINVAL;
+    DwLaunch L;
+    int rc = dw_resolve(c, L);
+    if (rc == CAPE_OK && stage <= 1) rc = dw_contract(L, (hipStream_t)stream);
+    if (rc == CAPE_OK && stage != 1) rc = dw_reduce(L, (hipStream_t)stream);
+    return rc;
+}
 }  // namespace
 
 extern "C" int cape_gconv_fwd_plan(const cape_src_t *srcs, int32_t nsrc, int32_t N, int32_t Mo, int32_t F, int32_t plan[4]) {
@@ -965,104 +1137,38 @@ extern "C" int cape_gconv_fwd_bf16(const cape_src_t *srcs, int32_t nsrc, void *y
 extern "C" int64_t cape_gconv_dw_workspace_bytes(const cape_src_t *srcs, int32_t nsrc, int32_t N,
                                                  int32_t Mo, int32_t F) {
     if (!srcs || nsrc < 1 || nsrc > CAPE_MAX_SRC || N < 1 || Mo < 1 || F < 1) return CAPE_EINVAL;
+    // asked before dz (and with it the kernel) is known: the larger of the two tile plans a launch can end up with
     DwPlan pl;
     plan_dw(srcs, nsrc, N, Mo, F, pl);
-    long long need = pl.slab * pl.ngroups * pl.rsplit;
-    {   // whichever kernel the launch ends up taking (depends on dz and on the storage type too): the larger plan
-        plan_dw_plain(srcs, nsrc, N, Mo, F, true, pl);
-        const long long n2 = pl.slab * pl.ngroups * pl.rsplit;
-        need = n2 > need ? n2 : need;
-    }
-    return (int64_t)need * (int64_t)sizeof(float);
+    const long long generic = dw_workspace_need(pl);
+    plan_dw_plain(srcs, nsrc, N, Mo, F, true, pl);
+    return (int64_t)std::max(generic, dw_workspace_need(pl));
 }
-
-namespace {
-// does this launch run as dw_h2_kernel (fp16 two-piece operands)?  Decided from the arguments alone, identically by the plan
-// query, the contraction stage and the reduction stages (they must agree on the number of partial slabs)
-inline bool dw_takes_h2(const cape_src_t *srcs, int nsrc, const float *dz2, uint32_t dz2_mask, int Mo, int lddz, const cape_h2_dw_t *h2) {
-    if (!h2) return false;
-    DwParams p;
-    p.nsrc = nsrc;
-    p.dz2_mask = dz2 ? dz2_mask : 0u;
-    p.Mo = Mo; p.lddz = lddz;                                     // (what h2_dw_eligible reads besides the row bounds)
-    for (int i = 0; i < nsrc; ++i) p.s[i].ldx = srcs[i].ldx;
-    fill_h2_dw(p, h2);
-    return h2_dw_eligible(p);
-}
-int gconv_dw_plan_impl(const cape_src_t *srcs, int32_t nsrc, const float *dz, int64_t dz_sample_stride,
-                       int32_t lddz, const float *dz2, uint32_t dz2_mask, int32_t N, int32_t Mo, int32_t F,
-                       int32_t plan[4], bool bf16, const cape_h2_dw_t *h2 = nullptr) {
-    if (!srcs || nsrc < 1 || nsrc > CAPE_MAX_SRC || !dz || N < 1 || Mo < 1 || F < 1 || lddz < F || !plan) return CAPE_EINVAL;
-    DwPlan pl;
-    plan[0] = choose_dw(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, pl, bf16);
-    // (the narrow kernels are serial kernels: they keep the 512-slot plan even when the launch carries row bounds -- ADVICE r05)
-    const int nm = dw_narrow_mode(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, F, plan[0], bf16);
-    if (nm) {
-        plan[0] = nm;
-    } else if (plan[0] == 3 && !bf16 && dw_takes_h2(srcs, nsrc, dz2, dz2_mask, Mo, lddz, h2)) {
-        plan[0] = 4;
-        plan_dw_splits(N, Mo, pl, DW_SLOTS_PIPELINED);
-    }
-    plan[1] = pl.ct; plan[2] = pl.ft; plan[3] = pl.ngroups * pl.rsplit;
-    return CAPE_OK;
-}
-struct DwReduceParams;
-// what a launch would run, without running it (cape_gconv_dw_batch): its parameters, its per-layer plan, its kernel
-struct DwDescribe {
-    DwParams p;
-    DwPlan pl;
-    bool use_h2, v4;
-};
-int gconv_dw_stage_impl(const cape_src_t *srcs, int32_t nsrc, const float *dz,
-                        int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
-                        int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
-                        int64_t workspace_bytes, int32_t stage, void *stream, bool bf16,
-                        DwReduceParams *batch_rp = nullptr, int *batch_vec = nullptr, int *batch_blocks = nullptr,
-                        const cape_h2_dw_t *h2 = nullptr, DwDescribe *describe = nullptr);
-}  // namespace
 
 extern "C" int cape_gconv_dw_plan(const cape_src_t *srcs, int32_t nsrc, const float *dz, int64_t dz_sample_stride,
                                   int32_t lddz, const float *dz2, uint32_t dz2_mask, int32_t N, int32_t Mo, int32_t F,
                                   int32_t plan[4]) {
-    return gconv_dw_plan_impl(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, plan, false);
+    return dw_plan_query(dw_call(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, false), plan);
 }
 
 extern "C" int cape_gconv_dw_plan_h2(const cape_src_t *srcs, int32_t nsrc, const float *dz, int64_t dz_sample_stride,
                                      int32_t lddz, const float *dz2, uint32_t dz2_mask, int32_t N, int32_t Mo, int32_t F,
                                      const cape_h2_dw_t *h2, int32_t plan[4]) {
-    return gconv_dw_plan_impl(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, plan, false, h2);
-}
-
-extern "C" int cape_gconv_dw_stage_h2(const cape_src_t *srcs, int32_t nsrc, const float *dz,
-                                      int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
-                                      int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
-                                      int64_t workspace_bytes, int32_t stage, const cape_h2_dw_t *h2, void *stream) {
-    if (stage > 2) return CAPE_EINVAL;
-    return gconv_dw_stage_impl(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, accumulate, workspace,
-                               workspace_bytes, stage, stream, false, nullptr, nullptr, nullptr, h2);
+    return dw_plan_query(dw_call(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, false, h2), plan);
 }
 
 extern "C" int cape_gconv_dw_plan_bf16(const cape_src_t *srcs, int32_t nsrc, const void *dz, int64_t dz_sample_stride,
                                        int32_t lddz, const void *dz2, uint32_t dz2_mask, int32_t N, int32_t Mo, int32_t F,
                                        int32_t plan[4]) {
-    return gconv_dw_plan_impl(srcs, nsrc, (const float *)dz, dz_sample_stride, lddz, (const float *)dz2, dz2_mask, N, Mo, F, plan, true);
+    return dw_plan_query(dw_call(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, true), plan);
 }
 
-extern "C" int cape_gconv_dw_bf16(const cape_src_t *srcs, int32_t nsrc, const void *dz,
-                                  int64_t dz_sample_stride, int32_t lddz, const void *dz2, uint32_t dz2_mask,
-                                  int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
-                                  int64_t workspace_bytes, void *stream) {
-    return gconv_dw_stage_impl(srcs, nsrc, (const float *)dz, dz_sample_stride, lddz, (const float *)dz2, dz2_mask, N, Mo, F,
-                               accumulate, workspace, workspace_bytes, 0, stream, true);
-}
-
-extern "C" int cape_gconv_dw_stage_bf16(const cape_src_t *srcs, int32_t nsrc, const void *dz,
-                                        int64_t dz_sample_stride, int32_t lddz, const void *dz2, uint32_t dz2_mask,
-                                        int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
-                                        int64_t workspace_bytes, int32_t stage, void *stream) {
-    if (stage > 2) return CAPE_EINVAL;
-    return gconv_dw_stage_impl(srcs, nsrc, (const float *)dz, dz_sample_stride, lddz, (const float *)dz2, dz2_mask, N, Mo, F,
-                               accumulate, workspace, workspace_bytes, stage, stream, true);
+extern "C" int cape_gconv_dw_stage(const cape_src_t *srcs, int32_t nsrc, const float *dz,
+                                   int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
+                                   int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
+                                   int64_t workspace_bytes, int32_t stage, void *stream) {
+    return dw_run(dw_call(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, false, nullptr, accumulate, workspace,
+                          workspace_bytes), stage, stream);
 }
 
 extern "C" int cape_gconv_dw(const cape_src_t *srcs, int32_t nsrc, const float *dz,
@@ -1073,159 +1179,44 @@ extern "C" int cape_gconv_dw(const cape_src_t *srcs, int32_t nsrc, const float *
                                workspace_bytes, 0, stream);
 }
 
-extern "C" int cape_gconv_dw_stage(const cape_src_t *srcs, int32_t nsrc, const float *dz,
-                                   int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
-                                   int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
-                                   int64_t workspace_bytes, int32_t stage, void *stream) {
-    if (stage > 2) return CAPE_EINVAL;
-    return gconv_dw_stage_impl(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, accumulate, workspace,
-                               workspace_bytes, stage, stream, false);
+extern "C" int cape_gconv_dw_stage_h2(const cape_src_t *srcs, int32_t nsrc, const float *dz,
+                                      int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
+                                      int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
+                                      int64_t workspace_bytes, int32_t stage, const cape_h2_dw_t *h2, void *stream) {
+    return dw_run(dw_call(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, false, h2, accumulate, workspace,
+                          workspace_bytes), stage, stream);
 }
 
-namespace {
-int gconv_dw_stage_impl(const cape_src_t *srcs, int32_t nsrc, const float *dz,
-                        int64_t dz_sample_stride, int32_t lddz, const float *dz2, uint32_t dz2_mask,
-                        int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
-                        int64_t workspace_bytes, int32_t stage, void *stream, bool bf16,
-                        DwReduceParams *batch_rp, int *batch_vec, int *batch_blocks, const cape_h2_dw_t *h2, DwDescribe *describe) {
-    if (stage < 0 || stage > 3 || (stage == 3 && (!batch_rp || !batch_vec || !batch_blocks))) return CAPE_EINVAL;
-    if (!srcs || nsrc < 1 || nsrc > CAPE_MAX_SRC || !dz || N < 1 || Mo < 1 || F < 1 || lddz < F || !workspace)
-        return CAPE_EINVAL;
-    if (dz2_mask && !dz2) return CAPE_EINVAL;
-    DwPlan pl;
-    const int fam = choose_dw(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, pl, bf16);
-    const bool packed = fam == 2, plain = fam != 0, dw_split = fam == 3;
-    const int narrow = dw_narrow_mode(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, F, fam, bf16);
-    // one workgroup per CU (256 slots) for the pipelined two-piece kernel ONLY: the narrow kernels are serial ones and keep the
-    // 512-slot plan whether or not the launch carries row bounds (every stage and the plan query decide this identically)
-    const bool use_h2 = !narrow && !bf16 && dw_split && dw_takes_h2(srcs, nsrc, dz2, dz2_mask, Mo, lddz, h2);
-    if (use_h2) plan_dw_splits(N, Mo, pl, DW_SLOTS_PIPELINED);
-    const bool dzvec = dw_dz_vec(dz, dz_sample_stride, lddz, dz2, bf16 ? 2 : 4);
-    const long long need = pl.slab * pl.ngroups * pl.rsplit * (long long)sizeof(float);
-    if (workspace_bytes < need) return CAPE_EWORKSPACE;
-    DwParams p;
-    DwReduceParams rp;
-    p.nsrc = nsrc; rp.nsrc = nsrc;
-    int toff = 0;
-    long long poff = 0;
-    for (int i = 0; i < nsrc; ++i) {
-        if (!srcs[i].w) return CAPE_EINVAL;
-        int rc = fill_src(p.s[i], srcs[i], bf16 ? 2 : 4);
-        if (rc) return rc;
-        p.tile_off[i] = toff; p.part_off[i] = poff; rp.part_off[i] = poff;
-        toff += packed ? 0 : pl.ctiles[i] * pl.ftiles;
-        poff += (long long)srcs[i].C * F;
-        p.vstart[i] = packed ? pl.vstart[i] : 0;
-        rp.w[i] = const_cast<float *>(srcs[i].w); rp.wrs[i] = srcs[i].w_rs; rp.wcs[i] = srcs[i].w_cs;
-    }
-    p.tile_off[nsrc] = toff; p.part_off[nsrc] = poff; rp.part_off[nsrc] = poff;
-    p.vstart[nsrc] = packed ? pl.vstart[nsrc] : 0;
-    p.dz = dz; p.dz2 = dz2; p.dz2_mask = dz2 ? dz2_mask : 0u; p.dzs = dz_sample_stride; p.lddz = lddz;
-    p.dzvec = dzvec;
-    p.N = N; p.Mo = Mo; p.F = F; p.ftiles = pl.ftiles;
-    p.rsplit = pl.rsplit; p.rows_per_split = pl.rows_per_split;
-    p.ngroups = pl.ngroups; p.samples_per_group = pl.samples_per_group;
-    p.ws = (float *)workspace; p.slab = pl.slab;
-    fill_h2_dw(p, bf16 ? nullptr : h2);
-    if (describe) {
-        describe->p = p;
-        describe->pl = pl;
-        describe->use_h2 = use_h2;
-        describe->v4 = use_h2 && h2_dw_v4(p, pl.ct, pl.ft);
-        return CAPE_OK;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    dim3 grid((unsigned)(pl.ntiles * ((pl.ngroups * pl.rsplit + 7) / 8) * 8)), block(256);     // cape_map_dw_block
-    if (stage >= 2) {
-        // reduction only: the partial slabs of an earlier stage-1 call with the same arguments are in the workspace
-    } else if (narrow == 5) {                                   // narrow.h: same splits and slabs, tile 0's workgroups do all sources
-        CAPE_LAUNCH(dw_narrow_in_kernel, grid, block, 32768, st, p, narrow_lpr(F / 4), pl.ntiles);
-    } else if (narrow == 6) {
-        int sumC = 0;
-        for (int i = 0; i < nsrc; ++i) sumC += srcs[i].C;
-        CAPE_LAUNCH(dw_narrow_out_kernel, grid, block, 16384, st, p, narrow_lpr(sumC / 4), pl.ntiles);
-    } else if (use_h2) {
-        h2_dw_launch(p, pl.ct, pl.ft, grid, st);                // fp16 two-piece operands: same tiles, splits and slabs
-    } else if (bf16 && dw_split) {
-        if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((dw_split_kernel<64, 64, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ct == 64) CAPE_LAUNCH((dw_split_kernel<64, 128, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ft == 64) CAPE_LAUNCH((dw_split_kernel<128, 64, cape_bf16>), grid, block, 0, st, p);
-        else CAPE_LAUNCH((dw_split_kernel<128, 128, cape_bf16>), grid, block, 0, st, p);
-    } else if (bf16 && packed) {
-        if (pl.ft == 32) CAPE_LAUNCH((dw_packed_kernel<128, 32, 4, 1, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((dw_packed_kernel<64, 64, 2, 2, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ct == 64) CAPE_LAUNCH((dw_packed_kernel<64, 128, 2, 2, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ft == 64) CAPE_LAUNCH((dw_packed_kernel<128, 64, 2, 2, cape_bf16>), grid, block, 0, st, p);
-        else CAPE_LAUNCH((dw_packed_kernel<128, 128, 2, 2, cape_bf16>), grid, block, 0, st, p);
-    } else if (bf16 && plain) {
-        if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((dw_plain_kernel<64, 64, 2, 2, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ct == 64) CAPE_LAUNCH((dw_plain_kernel<64, 128, 2, 2, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ft == 64) CAPE_LAUNCH((dw_plain_kernel<128, 64, 2, 2, cape_bf16>), grid, block, 0, st, p);
-        else CAPE_LAUNCH((dw_plain_kernel<128, 128, 2, 2, cape_bf16>), grid, block, 0, st, p);
-    } else if (bf16) {
-        if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((gconv_dw_kernel<64, 64, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ct == 64) CAPE_LAUNCH((gconv_dw_kernel<64, 128, cape_bf16>), grid, block, 0, st, p);
-        else if (pl.ft == 64) CAPE_LAUNCH((gconv_dw_kernel<128, 64, cape_bf16>), grid, block, 0, st, p);
-        else CAPE_LAUNCH((gconv_dw_kernel<128, 128, cape_bf16>), grid, block, 0, st, p);
-    } else
-    if (packed) {
-        if (pl.ft == 32) CAPE_LAUNCH((dw_packed_kernel<128, 32, 4, 1>), grid, block, 0, st, p);
-        else if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((dw_packed_kernel<64, 64, 2, 2>), grid, block, 0, st, p);
-        else if (pl.ct == 64) CAPE_LAUNCH((dw_packed_kernel<64, 128, 2, 2>), grid, block, 0, st, p);
-        else if (pl.ft == 64) CAPE_LAUNCH((dw_packed_kernel<128, 64, 2, 2>), grid, block, 0, st, p);
-        else CAPE_LAUNCH((dw_packed_kernel<128, 128, 2, 2>), grid, block, 0, st, p);
-    } else if (plain && dw_split) {
-        if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((dw_split_kernel<64, 64>), grid, block, 0, st, p);
-        else if (pl.ct == 64) CAPE_LAUNCH((dw_split_kernel<64, 128>), grid, block, 0, st, p);
-        else if (pl.ft == 64) CAPE_LAUNCH((dw_split_kernel<128, 64>), grid, block, 0, st, p);
-        else CAPE_LAUNCH((dw_split_kernel<128, 128>), grid, block, 0, st, p);
-    } else if (plain) {
-        if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((dw_plain_kernel<64, 64, 2, 2>), grid, block, 0, st, p);
-        else if (pl.ct == 64) CAPE_LAUNCH((dw_plain_kernel<64, 128, 2, 2>), grid, block, 0, st, p);
-        else if (pl.ft == 64) CAPE_LAUNCH((dw_plain_kernel<128, 64, 2, 2>), grid, block, 0, st, p);
-        else CAPE_LAUNCH((dw_plain_kernel<128, 128, 2, 2>), grid, block, 0, st, p);
-    } else
-    if (pl.ct == 64 && pl.ft == 64) CAPE_LAUNCH((gconv_dw_kernel<64, 64>), grid, block, 0, st, p);
-    else if (pl.ct == 64) CAPE_LAUNCH((gconv_dw_kernel<64, 128>), grid, block, 0, st, p);
-    else if (pl.ft == 64) CAPE_LAUNCH((gconv_dw_kernel<128, 64>), grid, block, 0, st, p);
-    else CAPE_LAUNCH((gconv_dw_kernel<128, 128>), grid, block, 0, st, p);
-    CAPE_LAUNCH_CHECK();
-    if (stage == 1) return CAPE_OK;
-    rp.F = F; rp.nsplit = pl.ngroups * pl.rsplit; rp.accumulate = accumulate; rp.ws = (const float *)workspace; rp.slab = pl.slab;
-    long long total = poff;
-    int rblocks = (int)((total + 15) / 16);
-    // the float4 form sums a quad's splits serially: only when the slab alone fills the chip (>= 256 blocks of quads);
-    // small slabs with many splits (fine mesh levels) take the kernel that also spreads the splits over 16 lanes
-    bool rvec = (F & 3) == 0 && (pl.slab & 3) == 0 && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0 && total >= 262144;
-    for (int i = 0; i < nsrc; ++i)
-        rvec = rvec && srcs[i].w_cs == 1 && (srcs[i].w_rs & 3) == 0 && (reinterpret_cast<uintptr_t>(srcs[i].w) & 15) == 0;
-    if (stage == 3) {                  // describe the reduction instead of launching it (cape_gconv_dw_reduce_batch)
-        *batch_rp = rp;
-        *batch_vec = rvec ? 1 : 0;
-        *batch_blocks = rvec ? (int)((total / 4 + 255) / 256) : rblocks;
-        return CAPE_OK;
-    }
-    if (rvec) CAPE_LAUNCH(dw_reduce_vec_kernel, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, st, rp);
-    else CAPE_LAUNCH(dw_reduce_kernel, dim3(rblocks), dim3(256), 0, st, rp);
-    CAPE_LAUNCH_CHECK();
-    return CAPE_OK;
+extern "C" int cape_gconv_dw_stage_bf16(const cape_src_t *srcs, int32_t nsrc, const void *dz,
+                                        int64_t dz_sample_stride, int32_t lddz, const void *dz2, uint32_t dz2_mask,
+                                        int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
+                                        int64_t workspace_bytes, int32_t stage, void *stream) {
+    return dw_run(dw_call(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, true, nullptr, accumulate, workspace,
+                          workspace_bytes), stage, stream);
 }
-}  // namespace
 
+extern "C" int cape_gconv_dw_bf16(const cape_src_t *srcs, int32_t nsrc, const void *dz,
+                                  int64_t dz_sample_stride, int32_t lddz, const void *dz2, uint32_t dz2_mask,
+                                  int32_t N, int32_t Mo, int32_t F, int32_t accumulate, void *workspace,
+                                  int64_t workspace_bytes, void *stream) {
+    return cape_gconv_dw_stage_bf16(srcs, nsrc, dz, dz_sample_stride, lddz, dz2, dz2_mask, N, Mo, F, accumulate, workspace,
+                                    workspace_bytes, 0, stream);
+}
+
+// the slab reductions of several launches (each contracted before with the same arguments) as one grid
 extern "C" int cape_gconv_dw_reduce_batch(const cape_dw_item_t *items, int32_t nitems, void *stream) {
     if (!items || nitems < 1 || nitems > CAPE_MAX_DW_REDUCE_ITEMS) return CAPE_EINVAL;
     DwReduceBatch B;
     B.n = nitems;
     int off = 0;
     for (int i = 0; i < nitems; ++i) {
-        const cape_dw_item_t &t = items[i];
-        int blocks = 0;
-        const int rc = gconv_dw_stage_impl(t.srcs, t.nsrc, (const float *)t.dz, t.dz_sample_stride, t.lddz, (const float *)t.dz2,
-                                           t.dz2_mask, t.N, t.Mo, t.F, t.accumulate, t.workspace, t.workspace_bytes, 3, stream,
-                                           t.bf16 != 0, &B.it[i], &B.vec[i], &blocks, t.h2);
+        DwLaunch L;
+        const int rc = dw_resolve(dw_call(items[i]), L);
         if (rc) return rc;
+        B.it[i] = L.rp;
+        B.vec[i] = L.rvec ? 1 : 0;
         B.blk_off[i] = off;
-        off += blocks;
+        off += L.rblocks;
     }
     B.blk_off[nitems] = off;
     CAPE_LAUNCH(dw_reduce_batch_kernel, dim3((unsigned)off), dim3(256), 0, (hipStream_t)stream, B);
@@ -1319,20 +1310,18 @@ inline void dwb_plan(const DwbShape *sh, int n, std::vector<DwbLaunch> &out) {
 }
 
 // an item of the list: does it run dw_h2_kernel<128, 128, true>, and with which tiles and splits?
-inline int dwb_describe(const cape_dw_item_t &t, DwDescribe &d, DwbShape &s) {
+inline int dwb_describe(const cape_dw_item_t &t, DwLaunch &d, DwbShape &s) {
     if (t.bf16 || !t.h2) return CAPE_EINVAL;
-    const int rc = gconv_dw_stage_impl(t.srcs, t.nsrc, (const float *)t.dz, t.dz_sample_stride, t.lddz, (const float *)t.dz2,
-                                       t.dz2_mask, t.N, t.Mo, t.F, t.accumulate, t.workspace, t.workspace_bytes, 1, nullptr,
-                                       false, nullptr, nullptr, nullptr, t.h2, &d);
+    const int rc = dw_resolve(dw_call(t), d);
     if (rc) return rc;
-    if (!d.use_h2 || !d.v4 || t.nsrc > DWB_MAX_SEGS) return CAPE_EINVAL;
+    if (d.kernel != DW_H2 || !d.v4 || t.nsrc > DWB_MAX_SEGS) return CAPE_EINVAL;
     s.N = t.N; s.nseg = t.nsrc;
     s.tiles = d.pl.ntiles;
     s.ngroups = d.pl.ngroups; s.rsplit = d.pl.rsplit; s.rows_per_split = d.pl.rows_per_split;
     return CAPE_OK;
 }
 
-int dwb_prepare(const cape_dw_item_t *items, int nitems, std::vector<DwDescribe> &desc, std::vector<DwbShape> &sh,
+int dwb_prepare(const cape_dw_item_t *items, int nitems, std::vector<DwLaunch> &desc, std::vector<DwbShape> &sh,
                 std::vector<DwbLaunch> &launches) {
     if (!items || nitems < 1 || nitems > CAPE_MAX_DW_REDUCE_ITEMS) return CAPE_EINVAL;
     desc.resize(nitems);
@@ -1347,7 +1336,7 @@ int dwb_prepare(const cape_dw_item_t *items, int nitems, std::vector<DwDescribe>
 }  // namespace
 
 extern "C" int cape_gconv_dw_batch_plan(const cape_dw_item_t *items, int32_t nitems, int32_t *units, int32_t max_units, int32_t info[4]) {
-    std::vector<DwDescribe> desc;
+    std::vector<DwLaunch> desc;
     std::vector<DwbShape> sh;
     std::vector<DwbLaunch> launches;
     const int rc = dwb_prepare(items, nitems, desc, sh, launches);
@@ -1361,7 +1350,7 @@ extern "C" int cape_gconv_dw_batch_plan(const cape_dw_item_t *items, int32_t nit
         for (int x = 0; x < 8; ++x)
             for (int tk = 0; tk < L.n; ++tk) {
                 const int k = L.order[tk];
-                const DwDescribe &d = desc[L.first + k];
+                const DwLaunch &d = desc[L.first + k];
                 const DwbShape &c = sh[L.first + k];
                 const int spg = c.N / c.ngroups;
                 for (int j = L.start[x][tk]; j < L.start[x][tk + 1]; ++j, ++nunits) {
@@ -1383,7 +1372,7 @@ extern "C" int cape_gconv_dw_batch_plan(const cape_dw_item_t *items, int32_t nit
 }
 
 extern "C" int cape_gconv_dw_batch(const cape_dw_item_t *items, int32_t nitems, void *stream) {
-    std::vector<DwDescribe> desc;
+    std::vector<DwLaunch> desc;
     std::vector<DwbShape> sh;
     std::vector<DwbLaunch> launches;
     const int rc = dwb_prepare(items, nitems, desc, sh, launches);

@@ -157,6 +157,14 @@ struct DwParams {
 };
 static_assert(sizeof(DwParams) <= 3584, "kernel arguments: 4 KB including the hidden ones");
 
+// The kernel of a weight-gradient launch, as the plan queries report it (plan[0]).  choose_dw (gconv.hip) picks one of the first
+// four from the operands' layout; dw_resolve then moves a launch to the two-piece or a narrow kernel where it qualifies.
+enum DwKernelId {
+    DW_GENERIC = 0, DW_PLAIN = 1, DW_PACKED = 2, DW_SPLIT = 3,      // gconv_dw_ / dw_plain_ / dw_packed_ / dw_split_kernel
+    DW_H2 = 4,                                                      // dw_h2_kernel: every operand carries row bounds
+    DW_NARROW_IN = 5, DW_NARROW_OUT = 6,                            // narrow.h: <= NARROW_MAXC channels in all / <= 4 outputs
+};
+
 // Epilogue of one workgroup tile: rank-1 condition terms, bias + activation (or, in DUAL mode,
 // relu(acc) + acc2 with the ReLU sign bitmask), store.  Accumulator layout of the 32x32 MFMA:
 // col = lane & 31, row = (g & 3) + 8 * (g >> 2) + 4 * (lane >> 5).

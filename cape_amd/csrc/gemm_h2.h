@@ -912,11 +912,12 @@ inline bool h2_dw_v4(const DwParams &p, int ct, int ft) {
     return ok;
 }
 
-inline void h2_dw_launch(const DwParams &p, int ct, int ft, dim3 grid, hipStream_t st) {
+// v4: what h2_dw_v4 answered for this launch (dw_resolve asks once)
+inline void h2_dw_launch(const DwParams &p, int ct, int ft, bool v4, dim3 grid, hipStream_t st) {
     const dim3 block(256 * H2_DW_KG);
     // (128 x 128 tiles only: with a 64-wide operand the two wave pairs of a group get unequal shares -- measured 12.8 -> 18.4 us on
     // 128 x 64, 17.3 -> 26.2 on 64 x 128 -- and 64 x 64 gains nothing; 128 x 128: 64.1 -> 62.6, 37.1 -> 36.3, 34.3 -> 33.6 us)
-    if (h2_dw_v4(p, ct, ft)) {
+    if (v4) {
         CAPE_LAUNCH((dw_h2_kernel<128, 128, true>), grid, block, 0, st, p);
         return;
     }

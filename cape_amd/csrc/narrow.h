@@ -223,20 +223,20 @@ inline int narrow_lpr(int quads) {
     return l;
 }
 
-// which narrow form (0 = none, 5 = narrow input, 6 = narrow output) a weight-gradient launch of family ``fam`` takes
-inline int dw_narrow_mode(const cape_src_t *srcs, int nsrc, const float *dz, int64_t dz_sample_stride, int32_t lddz, const float *dz2,
-                          uint32_t dz2_mask, int F, int fam, bool bf16) {
+// which narrow form (0 = none, else DW_NARROW_IN / DW_NARROW_OUT) a weight-gradient launch of family ``fam`` takes; p: the
+// launch's operands (sources, dz, dz2_mask, F)
+inline int dw_narrow_mode(const DwParams &p, int fam, bool bf16) {
     static const int on = getenv("CAPE_NARROW") ? atoi(getenv("CAPE_NARROW")) : 1;       // 0: A/B against the tile kernels
-    if (!on || bf16 || fam == 0 || (dz2 && dz2_mask)) return 0;          // plain sources only (families 1..3), one gradient operand
+    if (!on || bf16 || fam == DW_GENERIC || p.dz2_mask) return 0;        // plain sources only (families 1..3), one gradient operand
     int sumC = 0;
     bool c4 = true, xal = true;
-    for (int i = 0; i < nsrc; ++i) {
-        sumC += srcs[i].C;
-        c4 = c4 && (srcs[i].C & 3) == 0;
-        xal = xal && (srcs[i].ldx & 3) == 0 && (srcs[i].x_sample_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(srcs[i].x) & 15) == 0;
+    for (int i = 0; i < p.nsrc; ++i) {
+        sumC += p.s[i].C;
+        c4 = c4 && (p.s[i].C & 3) == 0;
+        xal = xal && (p.s[i].ldx & 3) == 0 && (p.s[i].xs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.s[i].x) & 15) == 0;
     }
-    const bool dzal = (lddz & 3) == 0 && (dz_sample_stride & 3) == 0 && (reinterpret_cast<uintptr_t>(dz) & 15) == 0;
-    if (sumC <= NARROW_MAXC && (F & 3) == 0 && F >= 16 && F <= 256 && dzal) return 5;
-    if (F <= 4 && c4 && xal && sumC >= 16 && sumC <= 256) return 6;
+    const bool dzal = (p.lddz & 3) == 0 && (p.dzs & 3) == 0 && (reinterpret_cast<uintptr_t>(p.dz) & 15) == 0;
+    if (sumC <= NARROW_MAXC && (p.F & 3) == 0 && p.F >= 16 && p.F <= 256 && dzal) return DW_NARROW_IN;
+    if (p.F <= 4 && c4 && xal && sumC >= 16 && sumC <= 256) return DW_NARROW_OUT;
     return 0;
 }

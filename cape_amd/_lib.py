@@ -231,6 +231,11 @@ SIGNATURES = {
     "cape_point_distance_plan": (C.c_int, [_i32, _i32, _i32, C.POINTER(_i32)]),
     "cape_point_nearest_fwd": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _i32, _i32, _p, _p, _p, _i64, _p]),
     "cape_point_nearest_bwd": (C.c_int, [_p, _i32, _p, _i32, _p, _p, _p, _i32, _i32, _i32, _p, _i32, _p, _i32, _p, _i64, _p]),
+    "cape_scan_distance_compat_workspace_bytes": (_i64, [_i32, _i32, _i32, _i32]),
+    "cape_scan_nearest_compat_fwd": (C.c_int, [_p, _i32, _p, _p, _i32, _p, _i32, _f32, _p, _i32, _i32, _i32, _i32, _p, _p, _p, _p,
+                                               _i64, _p]),
+    "cape_point_nearest_compat_fwd": (C.c_int, [_p, _i32, _p, _i32, _p, _i32, _p, _i32, _f32, _p, _i32, _i32, _i32, _p, _p, _p, _i64,
+                                                _p]),
 }
 
 # bf16-storage variants with the argument list of their fp32 namesake (include/cape_hip.h, last section)

@@ -13,8 +13,13 @@
 //                   struct Args (what the members read; built by the kernel from its own arguments),
 //                   load_query(a, n, i, x, y, z), stage(a, tile, n, t0, nt), d2(x, y, z, r) -> fp32 squared distance
 //   finish policy   struct Args, write(a, n, idx, valid, id): the outputs of query idx of sample n -- `valid` false: a padding row
+//   query extras    a search policy may name a struct Extra (default-constructible): per-query registers beyond the position,
+//                   such as a normal.  Its members then read load_query(a, n, i, x, y, z, extra) and d2(a, x, y, z, extra, r);
+//                   a policy without one is called as above and compiles to what it compiled to before the extras existed.
 // Which side `count` limits is two numbers per sample: the valid queries and the valid targets.  Rows beyond either are never read.
 #pragma once
+#include <type_traits>
+
 #include "../common.h"
 
 namespace nearest {
@@ -70,15 +75,31 @@ __device__ __forceinline__ int clamp_count(const int *count, long long n, int M)
     return c < 0 ? 0 : (c > M ? M : c);
 }
 
+struct NoExtra {};
+template <class P, class = void>
+struct query_extra {
+    using type = NoExtra;
+    static constexpr bool present = false;
+};
 template <class P>
-__device__ __forceinline__ void test_target(const float4 *tile, int j, int id, const float (&qx)[P::QPT], const float (&qy)[P::QPT],
-                                            const float (&qz)[P::QPT], float (&best)[P::QPT], int (&bid)[P::QPT]) {
+struct query_extra<P, std::void_t<typename P::Extra>> {
+    using type = typename P::Extra;
+    static constexpr bool present = true;
+};
+
+template <class P>
+__device__ __forceinline__ void test_target(const typename P::Args &a, const float4 *tile, int j, int id, const float (&qx)[P::QPT],
+                                            const float (&qy)[P::QPT], const float (&qz)[P::QPT],
+                                            const typename query_extra<P>::type (&qe)[P::QPT], float (&best)[P::QPT],
+                                            int (&bid)[P::QPT]) {
     float4 r[P::REC];
 #pragma unroll
     for (int c = 0; c < P::REC; ++c) r[c] = tile[P::REC * j + c];
 #pragma unroll
     for (int k = 0; k < P::QPT; ++k) {
-        const float d = P::d2(qx[k], qy[k], qz[k], r);
+        float d;
+        if constexpr (query_extra<P>::present) d = P::d2(a, qx[k], qy[k], qz[k], qe[k], r);
+        else d = P::d2(qx[k], qy[k], qz[k], r);
         if (d < best[k]) {                                                  // strict: the lowest id among ties, never a NaN
             best[k] = d;
             bid[k] = id;
@@ -100,11 +121,15 @@ __device__ __forceinline__ void nearest_search(const typename P::Args &a, float4
     if (i0 >= valid_queries) return;                                        // the whole workgroup: no barrier is left waiting
     float qx[P::QPT], qy[P::QPT], qz[P::QPT], best[P::QPT];
     int bid[P::QPT];
+    typename query_extra<P>::type qe[P::QPT];
 #pragma unroll
     for (int k = 0; k < P::QPT; ++k) {
         const int i = i0 + k * SB + threadIdx.x;
         qx[k] = qy[k] = qz[k] = 0.0f;
-        if (i < valid_queries) P::load_query(a, n, i, qx[k], qy[k], qz[k]);
+        if (i < valid_queries) {
+            if constexpr (query_extra<P>::present) P::load_query(a, n, i, qx[k], qy[k], qz[k], qe[k]);
+            else P::load_query(a, n, i, qx[k], qy[k], qz[k]);
+        }
         best[k] = __builtin_inff();
         bid[k] = -1;
     }
@@ -120,9 +145,9 @@ __device__ __forceinline__ void nearest_search(const typename P::Args &a, float4
         __syncthreads();
         if constexpr (P::UNROLL > 0) {
 #pragma unroll P::UNROLL
-            for (int j = 0; j < nt; ++j) test_target<P>(tile, j, t0 + j, qx, qy, qz, best, bid);
+            for (int j = 0; j < nt; ++j) test_target<P>(a, tile, j, t0 + j, qx, qy, qz, qe, best, bid);
         } else {
-            for (int j = 0; j < nt; ++j) test_target<P>(tile, j, t0 + j, qx, qy, qz, best, bid);
+            for (int j = 0; j < nt; ++j) test_target<P>(a, tile, j, t0 + j, qx, qy, qz, qe, best, bid);
         }
     }
 #pragma unroll

@@ -18,6 +18,9 @@
 // fewer, larger workgroups fill the part worse when the grid is small.  The compiler reports 48 / 51 / 94 VGPRs: the register
 // file does not decide.  DESIGN 7j has the figures.
 //
+// The normal-compatible forward (cape_point_nearest_compat_fwd) stages a second float4 per point, its normal, and
+// leaves the points whose normal disagrees with the query's out of the minimum; finish and backward are shared.
+//
 // Backward, one or two launches, no atomics.  (1) per query: dq = 2 g (q - p_index) in fp64, rounded once, and -- when dp is
 // wanted -- its negative as three doubles into the workspace.  (2) one thread per (sample, point): workgroups of points stream
 // the sample's indices through LDS in query order and add the record where the index is theirs: fixed-order fp64 sums, the same
@@ -85,6 +88,59 @@ __global__ __launch_bounds__(SB) void point_search_kernel(const float *q, int ld
     const long long n = blockIdx.x / (tiles * split);
     const PointSearch::Args a = {q, ldq, pts, ldp, Q, M};
     nearest_search<PointSearch>(a, tile, n, Q, Q, clamp_count(count, n, M), tiles, split, tiles_per_part, NQ, cand);
+}
+
+// The normal-compatible search: both sides carry a normal, and a point takes part in the minimum only if
+// c = fma(qn.z, pn.z, fma(qn.y, pn.y, qn.x pn.x)) >= cos_min in fp32 -- `d = compatible ? d : inf` in front of the skeleton's
+// strict `<`.  The staged point is two float4: the position, and the normal in what is padding in the plain tile (a second LDS
+// broadcast per test).  Normals are used as given; one with a component that is not finite is held as NaN on either side and is
+// compatible with nothing.
+struct PointSearchCompat {
+    static constexpr int QPT = ::QPT, TILE = PT, REC = 2, UNROLL = 4;
+    using Row = long long;
+    struct Extra {
+        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    };
+    struct Args {
+        PointSearch::Args s;
+        const float *qn;
+        int ldqn;
+        const float *pn;
+        int ldpn;
+        float cos_min;
+    };
+    static __device__ __forceinline__ void load_query(const Args &a, long long n, int j, float &qx, float &qy, float &qz, Extra &e) {
+        PointSearch::load_query(a.s, n, j, qx, qy, qz);
+        const float *s = a.qn + (n * a.s.Q + j) * a.ldqn;
+        const bool ok = isfinite(s[0]) && isfinite(s[1]) && isfinite(s[2]);
+        e.nx = ok ? s[0] : __builtin_nanf("");
+        e.ny = s[1];
+        e.nz = s[2];
+    }
+    static __device__ __forceinline__ void stage(const Args &a, float4 *tile, long long n, int i0, int np) {
+        for (int i = threadIdx.x; i < np; i += SB) {
+            const float *s = a.s.pts + (n * a.s.M + i0 + i) * a.s.ldp, *m = a.pn + (n * a.s.M + i0 + i) * a.ldpn;
+            const bool ok = isfinite(m[0]) && isfinite(m[1]) && isfinite(m[2]);
+            tile[2 * i] = make_float4(s[0], s[1], s[2], 0.0f);
+            tile[2 * i + 1] = make_float4(ok ? m[0] : __builtin_nanf(""), m[1], m[2], 0.0f);
+        }
+    }
+    static __device__ __forceinline__ float d2(const Args &a, float qx, float qy, float qz, const Extra &e, const float4 (&p)[2]) {
+        const float dx = qx - p[0].x, dy = qy - p[0].y, dz = qz - p[0].z;
+        const float d = __fmaf_rn(dz, dz, __fmaf_rn(dy, dy, dx * dx));
+        const float c = __fmaf_rn(e.nz, p[1].z, __fmaf_rn(e.ny, p[1].y, e.nx * p[1].x));
+        return c >= a.cos_min ? d : __builtin_inff();                       // a NaN c is compatible with nothing
+    }
+};
+
+__global__ __launch_bounds__(SB) void point_search_compat_kernel(const float *q, int ldq, const float *pts, int ldp, const float *qn,
+                                                                 int ldqn, const float *pn, int ldpn, float cos_min,
+                                                                 const int *count, int Q, int M, int tiles, int split,
+                                                                 int tiles_per_part, long long NQ, uint2 *cand) {
+    __shared__ float4 tile[PT * 2];
+    const long long n = blockIdx.x / (tiles * split);
+    const PointSearchCompat::Args a = {{q, ldq, pts, ldp, Q, M}, qn, ldqn, pn, ldpn, cos_min};
+    nearest_search<PointSearchCompat>(a, tile, n, Q, Q, clamp_count(count, n, M), tiles, split, tiles_per_part, NQ, cand);
 }
 
 // ---- forward (2): the fp64 evaluation of the winner; none, or one whose fp64 distance is not finite: index -1, d2 NaN -----------
@@ -226,6 +282,30 @@ extern "C" int cape_point_nearest_fwd(const float *q, int32_t ldq, const float *
         [&](dim3 grid, dim3 block) {
             CAPE_LAUNCH(point_search_kernel, grid, block, 0, st, q, ldq, points, ldp, count, Q, M, p.tiles, p.split,
                         p.tiles_per_part, (long long)N * Q, cand);
+        },
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(point_finish_kernel, grid, block, 0, st, q, ldq, points, ldp, (const uint2 *)cand, p.split, N, Q, M, index,
+                        d2);
+        });
+}
+
+// the workspace is the plain entry's: cape_point_distance_workspace_bytes
+extern "C" int cape_point_nearest_compat_fwd(const float *q, int32_t ldq, const float *points, int32_t ldp,
+                                             const float *query_normals, int32_t ldqn, const float *point_normals, int32_t ldpn,
+                                             float cos_min, const int32_t *count, int32_t N, int32_t Q, int32_t M, int32_t *index,
+                                             float *d2, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!q || !points || !query_normals || !point_normals || !index || !d2 || !workspace) return CAPE_EINVAL;
+    if (!sizes_ok(N, Q, M) || ldq < 3 || ldp < 3 || ldqn < 3 || ldpn < 3 || cos_min != cos_min) return CAPE_EINVAL;
+    const Plan p = point_plan(N, Q, M);
+    const long long groups = search_groups(N, p);
+    if (!launch_ok(workspace, workspace_bytes, fwd_bytes(N, Q, M), groups)) return CAPE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    uint2 *cand = (uint2 *)workspace;
+    return forward(
+        groups, (long long)N * Q,
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(point_search_compat_kernel, grid, block, 0, st, q, ldq, points, ldp, query_normals, ldqn, point_normals,
+                        ldpn, cos_min, count, Q, M, p.tiles, p.split, p.tiles_per_part, (long long)N * Q, cand);
         },
         [&](dim3 grid, dim3 block) {
             CAPE_LAUNCH(point_finish_kernel, grid, block, 0, st, q, ldq, points, ldp, (const uint2 *)cand, p.split, N, Q, M, index,

@@ -13,6 +13,10 @@
 // faces through LDS in tiles of FT records, regions chosen by selects.  (3) finish: nearest.h's merge, and the winner is
 // evaluated again in fp64 from the original fp32 coordinates: fp32 in and out, fp64 in between.
 //
+// The normal-compatible forward (cape_scan_nearest_compat_fwd) is the same three launches with an 80-byte record that
+// also holds the face's unit normal, and a search policy that keeps the point's normal in registers and leaves the faces whose
+// normal disagrees out of the minimum; finish and backward are shared.
+//
 // Backward, two launches, no atomics.  (1) per point: the corner ids of its face, the coefficients -2 g b_k and r = p - foot
 // (fp64, foot = a + b_1 (b - a) + b_2 (c - a) from the saved barycentrics), and dp = 2 g r when wanted.  (2) one thread per
 // (sample, vertex): workgroups of vertices stream the sample's corner ids through LDS in point order and add coef_k r in fp64
@@ -29,6 +33,7 @@ constexpr int FT = 512;             // faces per LDS tile (32 KB of records)
 constexpr int TARGET_WG = 512;      // split until about this many workgroups exist (two per compute unit)
 constexpr int GT = 1024;            // points per LDS tile of the gather
 constexpr int64_t REC_BYTES = 64;   // a face record
+constexpr int64_t REC_COMPAT_BYTES = 80;   // with the face's unit normal: the normal-compatible search (40 KB of records per tile)
 constexpr int64_t PAY = 6;          // doubles per point of the backward: 3 coefficients, r
 
 inline Plan scan_plan(int64_t N, int64_t F, int64_t M) { return make_plan(N, M, PB, F, FT, TARGET_WG, SPLIT_MAX); }
@@ -40,6 +45,9 @@ inline bool sizes_ok(int64_t N, int64_t V, int64_t F, int64_t M) {
 }
 
 inline int64_t fwd_bytes(int64_t N, int64_t F, int64_t M) { return N * F * REC_BYTES + cand_bytes(N, M, scan_plan(N, F, M)); }
+inline int64_t fwd_compat_bytes(int64_t N, int64_t F, int64_t M) {
+    return N * F * REC_COMPAT_BYTES + cand_bytes(N, M, scan_plan(N, F, M));
+}
 inline int64_t bwd_bytes(int64_t N, int64_t M) { return N * M * (16 + PAY * 8); }
 
 struct d3 {
@@ -51,29 +59,51 @@ __device__ __forceinline__ d3 sub(d3 a, d3 b) { return {a.x - b.x, a.y - b.y, a.
 __device__ __forceinline__ double dot(d3 a, d3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
 
 // ---- forward (1): face records -------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(LB) void scan_face_record_kernel(const float *x, int ldx, const int *faces, int N, int V, int F,
-                                                              float4 *rec) {
+// R float4 per record: 4 for the plain search; 5 for the normal-compatible one, whose fifth is the face's unit normal -- from the
+// ORIGINAL fp32 corners in fp64, rounded once (the rounded local corners would tilt a sliver's normal), (0, 0, 0) where
+// |u x v|^2 is zero or not finite
+template <int R>
+__device__ __forceinline__ void face_records(const float *x, int ldx, const int *faces, int N, int V, int F, float4 *rec) {
     const long long total = (long long)N * F;
     for (long long i = (long long)blockIdx.x * LB + threadIdx.x; i < total; i += (long long)gridDim.x * LB) {
         const int f = (int)(i % F);
         const long long n = i / F;
         const float *xs = x + n * V * ldx;
         const d3 o = load3(xs);
-        d3 c[3];
+        d3 g[3], c[3];
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            const d3 l = sub(load3(xs + (long long)faces[3 * f + k] * ldx), o);
+            g[k] = load3(xs + (long long)faces[3 * f + k] * ldx);
+            const d3 l = sub(g[k], o);
             c[k] = {(double)(float)l.x, (double)(float)l.y, (double)(float)l.z};       // the local fp32 mesh the search sees
         }
         const d3 u = sub(c[1], c[0]), v = sub(c[2], c[0]), e = sub(c[2], c[1]);
         const double bb = dot(u, u), bc = dot(u, v), cc = dot(v, v), ee = dot(e, e);
         const double den = bb * cc - bc * bc;
-        float4 *r = rec + i * 4;
+        float4 *r = rec + i * R;
         r[0] = make_float4((float)c[0].x, (float)c[0].y, (float)c[0].z, (float)bb);
         r[1] = make_float4((float)u.x, (float)u.y, (float)u.z, (float)bc);
         r[2] = make_float4((float)v.x, (float)v.y, (float)v.z, (float)cc);
         r[3] = make_float4((float)(1.0 / bb), (float)(1.0 / cc), (float)(1.0 / ee), (float)(1.0 / den));
+        if constexpr (R == 5) {
+            const d3 gu = sub(g[1], g[0]), gv = sub(g[2], g[0]);
+            const d3 m = {gu.y * gv.z - gu.z * gv.y, gu.z * gv.x - gu.x * gv.z, gu.x * gv.y - gu.y * gv.x};
+            const double mm = dot(m, m);
+            const double s = (mm > 0.0 && isfinite(mm)) ? 1.0 / sqrt(mm) : 0.0;
+            r[4] = s > 0.0 ? make_float4((float)(m.x * s), (float)(m.y * s), (float)(m.z * s), 0.0f)
+                           : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        }
     }
+}
+
+__global__ __launch_bounds__(LB) void scan_face_record_kernel(const float *x, int ldx, const int *faces, int N, int V, int F,
+                                                              float4 *rec) {
+    face_records<4>(x, ldx, faces, N, V, F, rec);
+}
+
+__global__ __launch_bounds__(LB) void scan_face_record_compat_kernel(const float *x, int ldx, const int *faces, int N, int V, int F,
+                                                                     float4 *rec) {
+    face_records<5>(x, ldx, faces, N, V, F, rec);
 }
 
 // ---- forward (2): the fp32 search ------------------------------------------------------------------------------------------------
@@ -144,6 +174,51 @@ __global__ __launch_bounds__(SB) void scan_search_kernel(const float4 *rec, cons
     const long long n = blockIdx.x / (tiles * split);
     const ScanSearch::Args a = {rec, pts, ldp, F, M, load3(x + n * V * ldx)};
     nearest_search<ScanSearch>(a, tile, n, M, clamp_count(count, n, M), F, tiles, split, tiles_per_part, NM, cand);
+}
+
+// The normal-compatible search: the point carries a normal, the 80-byte record the face's, and a face takes part in the minimum
+// only if c = fma(nz, fz, fma(ny, fy, nx fx)) >= cos_min in fp32 -- `d = compatible ? d : inf` in front of the skeleton's strict
+// `<`, so ties, the split and the merge stay what they are.  Normals are used as given (not normalised); a point normal with a
+// component that is not finite is held as NaN and is compatible with nothing.
+struct ScanSearchCompat {
+    static constexpr int QPT = PPT, TILE = FT, REC = 5, UNROLL = 0;
+    using Row = int;
+    struct Extra {
+        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+    };
+    struct Args {
+        ScanSearch::Args s;
+        const float *nrm;
+        int ldn;
+        float cos_min;
+    };
+    static __device__ __forceinline__ void load_query(const Args &a, long long n, int i, float &px, float &py, float &pz, Extra &e) {
+        ScanSearch::load_query(a.s, n, i, px, py, pz);
+        const float *s = a.nrm + (n * a.s.M + i) * a.ldn;
+        const bool ok = isfinite(s[0]) && isfinite(s[1]) && isfinite(s[2]);
+        e.nx = ok ? s[0] : __builtin_nanf("");
+        e.ny = s[1];
+        e.nz = s[2];
+    }
+    static __device__ __forceinline__ void stage(const Args &a, float4 *tile, long long n, int f0, int nf) {
+        const float4 *src = a.s.rec + (n * a.s.F + f0) * 5;
+        for (int j = threadIdx.x; j < nf * 5; j += SB) tile[j] = src[j];
+    }
+    static __device__ __forceinline__ float d2(const Args &a, float px, float py, float pz, const Extra &e, const float4 (&r)[5]) {
+        const float d = tri_d2(px, py, pz, r[0], r[1], r[2], r[3]);
+        const float c = __fmaf_rn(e.nz, r[4].z, __fmaf_rn(e.ny, r[4].y, e.nx * r[4].x));
+        return c >= a.cos_min ? d : __builtin_inff();                       // a NaN c is compatible with nothing
+    }
+};
+
+__global__ __launch_bounds__(SB) void scan_search_compat_kernel(const float4 *rec, const float *x, int ldx, const float *pts, int ldp,
+                                                                const float *nrm, int ldn, float cos_min, const int *count, int V,
+                                                                int F, int M, int tiles, int split, int tiles_per_part,
+                                                                long long NM, uint2 *cand) {
+    __shared__ float4 tile[FT * 5];
+    const long long n = blockIdx.x / (tiles * split);
+    const ScanSearchCompat::Args a = {{rec, pts, ldp, F, M, load3(x + n * V * ldx)}, nrm, ldn, cos_min};
+    nearest_search<ScanSearchCompat>(a, tile, n, M, clamp_count(count, n, M), F, tiles, split, tiles_per_part, NM, cand);
 }
 
 // ---- forward (3): merge and the fp64 evaluation of the winner -------------------------------------------------------------------
@@ -326,6 +401,39 @@ extern "C" int cape_scan_nearest_fwd(const float *x, int32_t ldx, const int32_t 
         [&](dim3 grid, dim3 block) {
             CAPE_LAUNCH(scan_search_kernel, grid, block, 0, st, (const float4 *)rec, x, ldx, points, ldp, count, V, F, M, p.tiles,
                         p.split, p.tiles_per_part, (long long)N * M, cand);
+        },
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(scan_finish_kernel, grid, block, 0, st, x, ldx, faces, points, ldp, count, (const uint2 *)cand, p.split, N,
+                        V, M, face, bary, d2);
+        });
+}
+
+extern "C" int64_t cape_scan_distance_compat_workspace_bytes(int32_t N, int32_t V, int32_t F, int32_t M) {
+    if (!sizes_ok(N, V, F, M)) return CAPE_EINVAL;
+    const int64_t a = fwd_compat_bytes(N, F, M), b = bwd_bytes(N, M);
+    return a > b ? a : b;
+}
+
+extern "C" int cape_scan_nearest_compat_fwd(const float *x, int32_t ldx, const int32_t *faces, const float *points, int32_t ldp,
+                                            const float *normals, int32_t ldn, float cos_min, const int32_t *count, int32_t N,
+                                            int32_t V, int32_t F, int32_t M, int32_t *face, float *bary, float *d2, void *workspace,
+                                            int64_t workspace_bytes, void *stream) {
+    if (!x || !faces || !points || !normals || !face || !bary || !d2 || !workspace) return CAPE_EINVAL;
+    if (!sizes_ok(N, V, F, M) || ldx < 3 || ldp < 3 || ldn < 3 || cos_min != cos_min) return CAPE_EINVAL;
+    const Plan p = scan_plan(N, F, M);
+    const long long groups = search_groups(N, p);
+    if (!launch_ok(workspace, workspace_bytes, fwd_compat_bytes(N, F, M), groups)) return CAPE_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    float4 *rec = (float4 *)workspace;
+    uint2 *cand = (uint2 *)((char *)workspace + (int64_t)N * F * REC_COMPAT_BYTES);
+    CAPE_LAUNCH(scan_face_record_compat_kernel, dim3(cape_grid_blocks((long long)N * F, LB, MAXB)), dim3(LB), 0, st, x, ldx, faces, N,
+                V, F, rec);
+    CAPE_LAUNCH_CHECK();
+    return forward(
+        groups, (long long)N * M,
+        [&](dim3 grid, dim3 block) {
+            CAPE_LAUNCH(scan_search_compat_kernel, grid, block, 0, st, (const float4 *)rec, x, ldx, points, ldp, normals, ldn,
+                        cos_min, count, V, F, M, p.tiles, p.split, p.tiles_per_part, (long long)N * M, cand);
         },
         [&](dim3 grid, dim3 block) {
             CAPE_LAUNCH(scan_finish_kernel, grid, block, 0, st, x, ldx, faces, points, ldp, count, (const uint2 *)cand, p.split, N,

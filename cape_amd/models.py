@@ -1937,7 +1937,7 @@ class CAPE(base_model):
 
     def fit_scan(self, scan, pose, cond, cond2, body_model, mean, std, clothing_idx, minimal_shape=None, transl=None, z0=None,
                  steps=200, lr=0.1, lambda_z=0.0, optimize_pose=False, optimize_transl=False, max_dist=None, lambda_mesh=0.0,
-                 mesh_weights=None, mesh_max_dist=None):
+                 mesh_weights=None, mesh_max_dist=None, scan_normals=None, normal_angle=None):
         """``fit_posed`` for raw scans -- points without correspondence: gradient descent (Adam) on ``z`` through
         decoder -> cape_smpl_dress -> SMPL posing -> scan-to-mesh distance (``SMPL.scan_distance_diff``: for every scan point
         the closest point of the posed surface, searched over all faces on the device at every step).
@@ -1964,12 +1964,22 @@ class CAPE(base_model):
         step's forward and is a constant of that step's gradient, and a distance that is NaN is dropped.  The scan is a
         constant: no gradient to its points is computed.  With ``lambda_mesh = 0`` nothing of this runs.
 
+        ``scan_normals`` and ``normal_angle``, both or neither, accept a correspondence only where the two normals agree
+        within ``normal_angle`` degrees (0 < normal_angle < 180) -- what keeps the two sides of a sleeve, or an arm
+        and the torso, from being pulled onto each other.  ``scan_normals`` has the form of ``scan`` (an array or a list) and
+        holds unit normals pointing out of the scanned surface; for a scan that is a mesh they are
+        ``VertexNormals(scan_faces, n).np(scan_verts)``.  A scan point searches only the faces whose normal has a cosine of at
+        least cos(normal_angle) with its own; with ``lambda_mesh > 0`` a vertex likewise searches only the scan points that
+        agree with its vertex normal (the posed mesh's, computed once per step, a constant of the gradient).  A point or
+        vertex without a compatible partner has a NaN distance and is dropped by the masks above, so ``inliers`` and
+        ``mesh_inliers`` keep their meaning.  Without ``scan_normals`` nothing of this is constructed or launched.
+
         Returns a dict: ``z``, ``pose``, ``transl``, ``posed``, ``clothed`` as ``fit_posed`` returns them, ``loss``
         [steps + 1, size] the scan-to-mesh term per sample (row 0: before the first update; the last row for the returned
         leaves) and ``inliers`` [steps + 1, size], the number of points under the mask; with ``lambda_mesh > 0`` also
         ``mesh_loss`` [steps + 1, size], the mesh-to-scan term before the multiplication by ``lambda_mesh``, and
         ``mesh_inliers`` [steps + 1, size], the number of vertices with a positive weight under its mask."""
-        from .scan_distance import pad_points
+        from .scan_distance import pad_normals, pad_points
         lambda_mesh = float(lambda_mesh)
         if not np.isfinite(lambda_mesh) or lambda_mesh < 0:
             raise ValueError("lambda_mesh must be finite and >= 0, got %r" % (lambda_mesh,))
@@ -1980,6 +1990,15 @@ class CAPE(base_model):
         body = getattr(body_model, 'model', body_model)
         pts, count = pad_points(scan)
         size, M, V, bs = pts.shape[0], pts.shape[1], body.V, self.batch_size
+        if (scan_normals is None) != (normal_angle is None):
+            raise ValueError("scan_normals and normal_angle: both or neither")
+        nrm = None
+        if scan_normals is not None:
+            normal_angle = float(normal_angle)
+            if not 0.0 < normal_angle < 180.0:
+                raise ValueError("normal_angle must lie in (0, 180) degrees, got %r" % (normal_angle,))
+            nrm = pad_normals("scan_normals", scan_normals, pts, count)
+            cos_min = float(np.cos(np.deg2rad(normal_angle)))
         if count is None:
             count = np.full(size, M, np.int32)
         mw = np.ones(V, np.float32) if mesh_weights is None else np.asarray(mesh_weights, dtype=np.float32)
@@ -2002,6 +2021,10 @@ class CAPE(base_model):
         def data_term(begin, end):
             nb = end - begin
             p = self._padded(pts, begin, end)
+            near_kw, mesh_kw = {}, {}
+            if nrm is not None:
+                pn = self._padded(nrm, begin, end)
+                near_kw, mesh_kw = dict(normals=pn, cos_min=cos_min), dict(point_normals=pn, cos_min=cos_min)
             cnt = np.zeros(bs, np.int32)                                                  # padded rows: no points
             cnt[:nb] = count[begin:end]
             counts = body._scan_distance().counts(cnt, bs, M)                             # checked and uploaded once
@@ -2012,7 +2035,8 @@ class CAPE(base_model):
                              **(dict(mesh_loss=torch.float32, mesh_inliers=torch.int32) if lambda_mesh else {}))
 
             def term(step, posed, want_grad):
-                d2 = body.scan_distance_diff(posed, p, counts) if want_grad else body.scan_distance(posed, p, counts)[0]
+                d2 = (body.scan_distance_diff(posed, p, counts, **near_kw) if want_grad
+                      else body.scan_distance(posed, p, counts, **near_kw)[0])
                 d = d2.detach()
                 mask = valid & (d <= limit)                                               # a NaN distance is no inlier
                 md = mask.double()
@@ -2021,7 +2045,8 @@ class CAPE(base_model):
                 roots, seeds = [d2], [(md * inv_m).float()]
                 if lambda_mesh:
                     # the same checked counts: a padded row has none, its vertices come back NaN and are dropped
-                    e2 = body.point_distance_diff(posed, p, counts) if want_grad else body.point_distance(posed, p, counts)[0]
+                    e2 = (body.point_distance_diff(posed, p, counts, **mesh_kw) if want_grad
+                          else body.point_distance(posed, p, counts, **mesh_kw)[0])
                     e = e2.detach()
                     near = e <= mesh_limit                                                # a NaN distance is no inlier
                     wm = near.double() * mw_dev

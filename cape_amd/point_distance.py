@@ -13,6 +13,11 @@ batch of query sets and clouds, and its gradient (cape_amd/csrc/scan/point_dista
 padding and is never read).  A point with a non-finite coordinate never wins; a query with a non-finite coordinate, a sample
 with ``count`` 0 and a sample without a finite point get index -1, d2 NaN and no gradient.  The gradient is that of d2 with the
 index held constant (exact wherever d2 is differentiable).  There is no CPU fallback.
+
+``forward``, ``diff`` and ``np`` also take ``query_normals`` [N, Q, 3], ``point_normals`` [N, M, 3] and ``cos_min``, all or none: a
+point then takes part in a query's minimum only if the dot product of the two normals (as given, not normalised) is at least
+``cos_min`` (decided in fp32 inside the search, cape_point_nearest_compat_fwd).  A query without a compatible point,
+and a normal with a non-finite component on either side, give index -1, d2 NaN and no gradient; normals take no gradient.
 """
 import ctypes as C
 
@@ -52,9 +57,32 @@ class PointDistance(NearestDistance):
         _, M, ldp = rows("points", points, dev, N=N)
         return N, Q, M, ldq, ldp
 
-    def _forward(self, queries, points, count, out):
+    _first_normals = "query_normals"
+
+    def forward(self, queries, points, count=None, out=None, query_normals=None, point_normals=None, cos_min=None):
+        """``NearestDistance.forward``; ``query_normals`` [N, Q, 3], ``point_normals`` [N, M, 3] (float32 on the device, by the
+        row rules of ``points``; the padding rows are never read) and ``cos_min``, all or none: only the points whose normal
+        has a dot product of at least ``cos_min`` with the query's take part (cape_point_nearest_compat_fwd)."""
+        return NearestDistance.forward(self, queries, points, count, out,
+                                       self._compat(cos_min, query_normals=query_normals, point_normals=point_normals))
+
+    __call__ = forward
+
+    def diff(self, queries, points, count=None, return_selection=False, query_normals=None, point_normals=None, cos_min=None):
+        """``NearestDistance.diff``; the normals and ``cos_min`` as in ``forward``.  Normals take no gradient."""
+        return NearestDistance.diff(self, queries, points, count, return_selection,
+                                    self._compat(cos_min, query_normals=query_normals, point_normals=point_normals))
+
+    def np(self, queries, points, query_normals=None, point_normals=None, cos_min=None):
+        """``NearestDistance.np``; ``query_normals`` in the shape of ``queries``, ``point_normals`` in the form of ``points``."""
+        return NearestDistance.np(self, queries, points, cos_min, query_normals=query_normals, point_normals=point_normals)
+
+    def _forward(self, queries, points, count, out, compat=None):
         dev = self._upload()[0]
         N, Q, M, ldq, ldp = self._sizes(queries, points, dev)
+        if compat is not None:
+            ldqn = self._normal_rows("query_normals", compat[1], N, Q, dev)
+            ldpn = self._normal_rows("point_normals", compat[2], N, M, dev)
         _, cnt = check_count(count, N, M, dev)
         if out is None:
             out = (torch.empty((N, Q), dtype=torch.float32, device=dev), torch.empty((N, Q), dtype=torch.int32, device=dev))
@@ -64,6 +92,11 @@ class PointDistance(NearestDistance):
         check_tensor("out d2", d2, torch.float32, (N, Q), dev)
         check_tensor("out index", index, torch.int32, (N, Q), dev)
         ws, need = self._workspace(dev, N, Q, M)
+        if compat is not None:
+            _lib.check(_lib.lib.cape_point_nearest_compat_fwd(_p(queries), ldq, _p(points), ldp, _p(compat[1]), ldqn, _p(compat[2]),
+                                                              ldpn, compat[0], _p(cnt), N, Q, M, _p(index), _p(d2), _p(ws), need,
+                                                              _stream()), "cape_point_nearest_compat_fwd")
+            return d2, index
         _lib.check(_lib.lib.cape_point_nearest_fwd(_p(queries), ldq, _p(points), ldp, _p(cnt), N, Q, M, _p(index), _p(d2), _p(ws),
                                                    need, _stream()), "cape_point_nearest_fwd")
         return d2, index

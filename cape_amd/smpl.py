@@ -390,19 +390,20 @@ class SMPL(object):
             self._scan = ScanDistance(self.faces, self.V, device=self._device)
         return self._scan
 
-    def scan_distance(self, verts, points, count=None, out=None):
+    def scan_distance(self, verts, points, count=None, out=None, normals=None, cos_min=None):
         """(d2 [N, M], face [N, M], bary [N, M, 3]): for every device scan point ``points`` [N, M, 3] the squared distance to,
         and the closest point on, the device meshes ``verts`` [N, V, 3] in the model's topology, as
-        ``cape_amd.scan_distance.ScanDistance.forward`` computes them (no gradient)."""
-        return self._scan_distance().forward(verts, points, count, out)
+        ``cape_amd.scan_distance.ScanDistance.forward`` computes them (no gradient).  ``normals`` [N, M, 3] and ``cos_min``,
+        both or neither: only the faces whose normal agrees with the point's that far are searched."""
+        return self._scan_distance().forward(verts, points, count, out, normals, cos_min)
 
-    def scan_distance_diff(self, verts, points, count=None):
+    def scan_distance_diff(self, verts, points, count=None, normals=None, cos_min=None):
         """``scan_distance``'s d2 as an autograd function: gradients on it flow to ``verts`` and ``points``."""
-        return self._scan_distance().diff(verts, points, count)
+        return self._scan_distance().diff(verts, points, count, normals=normals, cos_min=cos_min)
 
-    def scan_distance_np(self, verts, points):
-        """``scan_distance``, numpy in (``points`` an array or a list of [m_n, 3] arrays), numpy out."""
-        return self._scan_distance().np(verts, points)
+    def scan_distance_np(self, verts, points, normals=None, cos_min=None):
+        """``scan_distance``, numpy in (``points`` and ``normals`` an array or a list of [m_n, 3] arrays), numpy out."""
+        return self._scan_distance().np(verts, points, normals, cos_min)
 
     def _point_distance(self):
         """``PointDistance`` on the model's device, constructed on first use."""
@@ -411,19 +412,32 @@ class SMPL(object):
             self._point = PointDistance(device=self._device)
         return self._point
 
-    def point_distance(self, verts, points, count=None, out=None):
+    def _query_normals(self, verts, point_normals):
+        """The vertex normals of ``verts`` for the normal-compatible search (no gradient); None without ``point_normals``."""
+        if point_normals is None:
+            return None
+        with torch.no_grad():
+            return self.vertex_normals(verts.detach())
+
+    def point_distance(self, verts, points, count=None, out=None, point_normals=None, cos_min=None):
         """(d2 [N, V], index [N, V] int32): for every vertex of ``verts`` [N, V, 3] the squared distance to the nearest of
         ``points`` [N, M, 3] (``count`` [N]: how many rows of a sample are points) and that point's index, as
-        ``cape_amd.point_distance.PointDistance.forward`` computes them (no gradient)."""
-        return self._point_distance().forward(verts, points, count, out)
+        ``cape_amd.point_distance.PointDistance.forward`` computes them (no gradient).  ``point_normals`` [N, M, 3] and
+        ``cos_min``, both or neither: only the points whose normal agrees that far with the vertex's
+        (``vertex_normals(verts)``) are searched."""
+        return self._point_distance().forward(verts, points, count, out, self._query_normals(verts, point_normals),
+                                              point_normals, cos_min)
 
-    def point_distance_diff(self, verts, points, count=None):
-        """``point_distance``'s d2 as an autograd function: gradients on it flow to ``verts`` and ``points``."""
-        return self._point_distance().diff(verts, points, count)
+    def point_distance_diff(self, verts, points, count=None, point_normals=None, cos_min=None):
+        """``point_distance``'s d2 as an autograd function: gradients on it flow to ``verts`` and ``points``; the vertex
+        normals of the filter are constants."""
+        return self._point_distance().diff(verts, points, count, query_normals=self._query_normals(verts, point_normals),
+                                           point_normals=point_normals, cos_min=cos_min)
 
-    def point_distance_np(self, verts, points):
-        """``point_distance``, numpy in (``points`` an array or a list of [m_n, 3] arrays), numpy out."""
-        return self._point_distance().np(verts, points)
+    def point_distance_np(self, verts, points, point_normals=None, cos_min=None):
+        """``point_distance``, numpy in (``points`` and ``point_normals`` an array or a list of [m_n, 3] arrays), numpy out."""
+        qn = None if point_normals is None else self.vertex_normals_np(np.asarray(verts, dtype=np.float32).reshape(-1, self.V, 3))
+        return self._point_distance().np(verts, points, qn, point_normals, cos_min)
 
     def pose(self, verts, pose, betas=None, transl=None):
         """numpy in, numpy out: (vertices [N,V,3], joints [N,J,3]) float32."""

@@ -70,6 +70,9 @@
  *   cape_point_nearest_fwd / cape_point_nearest_bwd
  *                       no counterpart in the reference either: the opposite direction, for every mesh vertex the nearest
  *                       point of a raw scan (exact, over all points), and the gradient of the squared distance w.r.t. both.
+ *   cape_scan_nearest_compat_fwd / cape_point_nearest_compat_fwd
+ *                       the two searches over the normal-compatible targets only (the dot product of the two sides' normals at
+ *                       least cos_min): what registration pipelines use on thin parts and where surfaces touch.
  */
 #ifndef CAPE_HIP_H
 #define CAPE_HIP_H
@@ -1152,6 +1155,26 @@ int cape_scan_nearest_bwd(const float *x, int32_t ldx, const int32_t *faces, con
                           float *dx, int32_t ldd, float *dp, int32_t lddp, void *workspace, int64_t workspace_bytes, void *stream);
 
 /*
+ * cape_scan_nearest_compat_fwd: cape_scan_nearest_fwd with normal compatibility.  normals [N, M, 3] (leading dimension ldn >= 3,
+ * pad never read; rows i >= count[n] never read) is the scan points' normals; a face takes part in a point's minimum only if
+ *   c = fma(n.z, m.z, fma(n.y, m.y, n.x m.x)) >= cos_min          in fp32, n the point's normal as given (not normalised),
+ * m the face's unit normal (u x v) / |u x v| of u = b - a, v = c - a, taken in fp64 from the original fp32 corners and rounded
+ * once, (0, 0, 0) where |u x v|^2 is zero or not finite (such a face is compatible iff cos_min <= 0), whichever region of the
+ * rule the foot falls in.  A point whose normal has a component that is not finite is compatible with no face.  A point without
+ * a compatible finite face: face -1, d2 NaN, bary 0.  Everything else -- ties, the split, the merge, the fp64 evaluation of the
+ * winner (which does not decide compatibility again), padding rows -- is cape_scan_nearest_fwd's; with finite unit normals and
+ * cos_min <= -2 so are the bits.  The record is 80 bytes (the fifth float4 is m), so the workspace is larger:
+ * cape_scan_distance_compat_workspace_bytes(N, V, F, M), enough for cape_scan_nearest_bwd too, which serves unchanged (the
+ * selection is a constant of the gradient; normals take none).
+ * Errors: those of cape_scan_nearest_fwd, and CAPE_EINVAL for normals NULL, ldn < 3 or a NaN cos_min; all before any launch.
+ */
+int64_t cape_scan_distance_compat_workspace_bytes(int32_t N, int32_t V, int32_t F, int32_t M);
+int cape_scan_nearest_compat_fwd(const float *x, int32_t ldx, const int32_t *faces, const float *points, int32_t ldp,
+                                 const float *normals, int32_t ldn, float cos_min, const int32_t *count, int32_t N, int32_t V,
+                                 int32_t F, int32_t M, int32_t *face, float *bary, float *d2, void *workspace,
+                                 int64_t workspace_bytes, void *stream);
+
+/*
  * Mesh-to-scan distance (cape_amd/csrc/scan/point_distance.hip): for every query (a mesh vertex) the nearest point of a point
  * cloud (a scan), for a batch of query sets and clouds.  q [N, Q, 3] with leading dimension ldq >= 3 (pad never read), samples
  * Q rows apart, every row a query; points [N, M, 3] with leading dimension ldp >= 3 (pad never read), samples M rows apart;
@@ -1192,6 +1215,22 @@ int cape_point_nearest_fwd(const float *q, int32_t ldq, const float *points, int
 int cape_point_nearest_bwd(const float *q, int32_t ldq, const float *points, int32_t ldp, const int32_t *count,
                            const int32_t *index, const float *g, int32_t N, int32_t Q, int32_t M, float *dq, int32_t lddq,
                            float *dp, int32_t lddp, void *workspace, int64_t workspace_bytes, void *stream);
+
+/*
+ * cape_point_nearest_compat_fwd: cape_point_nearest_fwd with normal compatibility.  query_normals [N, Q, 3] (ldqn >= 3) and
+ * point_normals [N, M, 3] (ldpn >= 3; rows i >= count[n] never read), pads never read.  A point takes part in a query's minimum
+ * only if c = fma(a.z, b.z, fma(a.y, b.y, a.x b.x)) >= cos_min in fp32, a the query's normal and b the point's, both as given
+ * (not normalised).  A normal with a component that is not finite, on either side, is compatible with nothing.  A query without
+ * a compatible finite point: index -1, d2 NaN.  Everything else is cape_point_nearest_fwd's, and with finite unit normals and
+ * cos_min <= -2 so are the bits.  The staged point is two float4 (position, normal).  The workspace is
+ * cape_point_distance_workspace_bytes(N, Q, M); cape_point_nearest_bwd serves unchanged.
+ * Errors: those of cape_point_nearest_fwd, and CAPE_EINVAL for a NULL normals operand, ldqn or ldpn < 3 or a NaN cos_min; all
+ * before any launch.
+ */
+int cape_point_nearest_compat_fwd(const float *q, int32_t ldq, const float *points, int32_t ldp, const float *query_normals,
+                                  int32_t ldqn, const float *point_normals, int32_t ldpn, float cos_min, const int32_t *count,
+                                  int32_t N, int32_t Q, int32_t M, int32_t *index, float *d2, void *workspace,
+                                  int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -12,7 +12,10 @@ against --valu-peak instructions x lanes per second (default: the part's fp32 ve
 fused multiply-adds, 7.865e13; plain fp32 VALU instructions issue faster than 16 lanes per SIMD and clock here).
 With --fit: one ``CAPE.fit_scan`` step at batch 16 on a seeded model, M = 20000 points per scan, with ``lambda_mesh`` 0 and 1
 in alternating sets (--fit-rounds of them), each from calls of --fit-steps and 0 steps.
-Usage: python tools/point_distance_bench.py [--calls 50] [--torch-calls 20] [--fit] [--out FILE]"""
+With --cos-min C: also the normal-compatible forward (``query_normals`` = the meshes' vertex normals, ``point_normals`` = the
+sampled faces' normals, ``cos_min`` = C; cape_point_nearest_compat_fwd) next to the plain one, in alternating sets of the same
+run: ``fwd_plain_alt``, ``fwd_compat`` and their ratio ``compat_over_plain``.  --torch-calls 0 leaves the torch restatement out.
+Usage: python tools/point_distance_bench.py [--calls 50] [--torch-calls 20] [--cos-min C] [--fit] [--out FILE]"""
 import argparse
 import json
 import os
@@ -56,6 +59,26 @@ def _time_events(fn, calls, warmup):
         b.synchronize()
         ts.append(a.elapsed_time(b) * 1e3)
     return float(np.median(ts))
+
+
+def _time_alternating(fns, calls, warmup, sets=5):
+    """Median us per call of each of ``fns``, timed in ``sets`` alternating sets of calls / sets calls each: what drifts during the
+    run (clocks, temperature) reaches all of them alike."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(sets):
+        for k, fn in enumerate(fns):
+            for _ in range(max(1, calls // sets)):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ts[k].append(a.elapsed_time(b) * 1e3)
+    return [float(np.median(t)) for t in ts]
 
 
 def fit_steps(steps, M, rounds, seed=0):
@@ -113,6 +136,7 @@ def main():
     ap.add_argument("--points", default="20000")
     ap.add_argument("--chunk", type=int, default=1024)
     ap.add_argument("--valu-peak", type=float, default=157.3e12 / 2)
+    ap.add_argument("--cos-min", type=float, default=None)
     ap.add_argument("--fit", action="store_true")
     ap.add_argument("--fit-steps", type=int, default=20)
     ap.add_argument("--fit-rounds", type=int, default=3)
@@ -131,8 +155,8 @@ def main():
     for N in [int(x) for x in a.sizes.split(",")]:
         for M in [int(x) for x in a.points.split(",")]:
             xs = (verts[None] + 0.005 * rng.standard_normal((N, Q, 3))).astype(np.float32)
-            ps = np.stack([(lambda s: s[0] + rng.uniform(-0.01, 0.03, M)[:, None] * s[1])(
-                R.surface_samples(rng, xs[n].astype(np.float64), faces, M)) for n in range(N)]).astype(np.float32)
+            samples = [R.surface_samples(rng, xs[n].astype(np.float64), faces, M) for n in range(N)]
+            ps = np.stack([s[0] + rng.uniform(-0.01, 0.03, M)[:, None] * s[1] for s in samples]).astype(np.float32)
             x, p = torch.tensor(xs, device=dev), torch.tensor(ps, device=dev)
             g = torch.tensor(rng.standard_normal((N, Q)), dtype=torch.float32, device=dev)
             xg, pg = x.clone().requires_grad_(True), p.clone().requires_grad_(True)
@@ -153,21 +177,37 @@ def main():
 
             with torch.no_grad():
                 us_fwd = _time_events(lambda: pd.forward(x, p), a.calls, 10)
-                us_torch = _time_events(lambda: torch_points(x, p, a.chunk), a.torch_calls, 2)
-                d_hip, d_torch = pd.forward(x, p)[0], torch_points(x, p, a.chunk)
-                dmax = float((d_hip.sqrt() - d_torch.sqrt()).abs().max())
             us_fb = _time_events(fwd_bwd, a.calls, 10)
             g_hip = xg.grad.clone()
             us_fb_dp = _time_events(fwd_bwd_dp, a.calls, 10)
-            us_torch_fb = _time_events(torch_fwd_bwd, a.torch_calls, 2)
-            gdiff = float((xg.grad - g_hip).abs().max() / g_hip.abs().max())
             tests = float(N) * Q * M
             rate = lambda us: dict(us=round(us, 1), tests_per_s=float("%.4g" % (tests / us * 1e6)),
                                    valu_fraction=float("%.3g" % (tests * OPS_PER_TEST / (us * 1e-6) / a.valu_peak)))
-            rec = dict(tool="point_distance_bench", N=N, Q=Q, M=M, split=pd.plan(N, Q, M)[0], max_abs_dist_diff_vs_torch=dmax,
-                       grad_max_rel_diff_vs_torch=gdiff, fwd=rate(us_fwd), fwd_bwd=rate(us_fb), fwd_bwd_dp=rate(us_fb_dp),
-                       torch_fwd=rate(us_torch), torch_fwd_bwd=rate(us_torch_fb), speedup_fwd_vs_torch=round(us_torch / us_fwd, 1),
-                       speedup_fwd_bwd_vs_torch=round(us_torch_fb / us_fb, 1), calls=a.calls, torch_calls=a.torch_calls)
+            rec = dict(tool="point_distance_bench", N=N, Q=Q, M=M, split=pd.plan(N, Q, M)[0], fwd=rate(us_fwd), fwd_bwd=rate(us_fb),
+                       fwd_bwd_dp=rate(us_fb_dp), calls=a.calls, torch_calls=a.torch_calls)
+            if a.torch_calls > 0:
+                with torch.no_grad():
+                    us_torch = _time_events(lambda: torch_points(x, p, a.chunk), a.torch_calls, 2)
+                    d_hip, d_torch = pd.forward(x, p)[0], torch_points(x, p, a.chunk)
+                    dmax = float((d_hip.sqrt() - d_torch.sqrt()).abs().max())
+                xg.grad = None
+                fwd_bwd()
+                g_hip = xg.grad.clone()
+                us_torch_fb = _time_events(torch_fwd_bwd, a.torch_calls, 2)
+                gdiff = float((xg.grad - g_hip).abs().max() / g_hip.abs().max())
+                rec.update(max_abs_dist_diff_vs_torch=dmax, grad_max_rel_diff_vs_torch=gdiff, torch_fwd=rate(us_torch),
+                           torch_fwd_bwd=rate(us_torch_fb), speedup_fwd_vs_torch=round(us_torch / us_fwd, 1),
+                           speedup_fwd_bwd_vs_torch=round(us_torch_fb / us_fb, 1))
+            if a.cos_min is not None:
+                from cape_amd.vertex_normals import VertexNormals
+                pn = torch.tensor(np.stack([s[1] for s in samples]).astype(np.float32), device=dev)
+                with torch.no_grad():
+                    qn = VertexNormals(faces, Q, device=dev).forward(x)
+                    kw = dict(query_normals=qn, point_normals=pn, cos_min=a.cos_min)
+                    us_plain, us_compat = _time_alternating([lambda: pd.forward(x, p), lambda: pd.forward(x, p, **kw)], a.calls, 10)
+                    kept = int((pd.forward(x, p, **kw)[1] >= 0).sum())
+                rec.update(cos_min=a.cos_min, fwd_plain_alt=rate(us_plain), fwd_compat=rate(us_compat),
+                           compat_over_plain=round(us_compat / us_plain, 3), queries_with_a_point=kept)
             print(json.dumps(rec), flush=True)
             lines.append(rec)
     if a.fit:

@@ -7,7 +7,10 @@ host launch cost included):
              torch.where, min over the faces), chunked over --chunk points, without and with autograd (--torch-calls calls)
 ``tests_per_s``: point-triangle tests (N M F) per second of the call.  With --fit: one ``CAPE.fit_posed`` step and one
 ``CAPE.fit_scan`` step at batch 16 on a seeded model, M = 20000 points per scan, from calls of --fit-steps and 0 steps.
-Usage: python tools/scan_distance_bench.py [--calls 50] [--torch-calls 50] [--fit] [--out FILE]"""
+With --cos-min C: also the normal-compatible forward (``normals`` = the sampled faces' normals, ``cos_min`` = C;
+cape_scan_nearest_compat_fwd) next to the plain one, in alternating sets of the same run: ``fwd_plain_alt``, ``fwd_compat`` and
+their ratio ``compat_over_plain``.  --torch-calls 0 leaves the torch restatement out.
+Usage: python tools/scan_distance_bench.py [--calls 50] [--torch-calls 50] [--cos-min C] [--fit] [--out FILE]"""
 import argparse
 import json
 import os
@@ -68,6 +71,26 @@ def _time_events(fn, calls, warmup):
     return float(np.median(ts))
 
 
+def _time_alternating(fns, calls, warmup, sets=5):
+    """Median us per call of each of ``fns``, timed in ``sets`` alternating sets of calls / sets calls each: what drifts during the
+    run (clocks, temperature) reaches all of them alike."""
+    for fn in fns:
+        for _ in range(warmup):
+            fn()
+    torch.cuda.synchronize()
+    ts = [[] for _ in fns]
+    for _ in range(sets):
+        for k, fn in enumerate(fns):
+            for _ in range(max(1, calls // sets)):
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                fn()
+                b.record()
+                b.synchronize()
+                ts[k].append(a.elapsed_time(b) * 1e3)
+    return [float(np.median(t)) for t in ts]
+
+
 def fit_steps(steps, M, seed=0):
     """(us per fit_posed step, us per fit_scan step) at batch 16: the difference of a call with ``steps`` steps and one with
     none, both after a warm-up call."""
@@ -118,6 +141,7 @@ def main():
     ap.add_argument("--sizes", default="1,16")
     ap.add_argument("--points", default="2000,20000")
     ap.add_argument("--chunk", type=int, default=1024)
+    ap.add_argument("--cos-min", type=float, default=None)
     ap.add_argument("--fit", action="store_true")
     ap.add_argument("--fit-steps", type=int, default=20)
     ap.add_argument("--out", default=None)
@@ -136,9 +160,10 @@ def main():
     for N in [int(x) for x in a.sizes.split(",")]:
         for M in [int(x) for x in a.points.split(",")]:
             xs = (verts[None] + 0.005 * rng.standard_normal((N, V, 3))).astype(np.float32)
-            ps = np.stack([(lambda s: s[0] + rng.uniform(-0.01, 0.03, M)[:, None] * s[1])(
-                R.surface_samples(rng, xs[n].astype(np.float64), faces, M)) for n in range(N)]).astype(np.float32)
+            samples = [R.surface_samples(rng, xs[n].astype(np.float64), faces, M) for n in range(N)]
+            ps = np.stack([s[0] + rng.uniform(-0.01, 0.03, M)[:, None] * s[1] for s in samples]).astype(np.float32)
             x, p = torch.tensor(xs, device=dev), torch.tensor(ps, device=dev)
+            nrm = torch.tensor(np.stack([s[1] for s in samples]).astype(np.float32), device=dev)
             g = torch.tensor(rng.standard_normal((N, M)), dtype=torch.float32, device=dev)
             xg = x.clone().requires_grad_(True)
 
@@ -154,21 +179,31 @@ def main():
 
             with torch.no_grad():
                 us_fwd = _time_events(lambda: sd.forward(x, p), a.calls, 10)
-                us_torch = _time_events(lambda: torch_scan(x, ft, p, a.chunk), a.torch_calls, 2)
-                d_hip, d_torch = sd.forward(x, p)[0], torch_scan(x, ft, p, a.chunk)
-                dmax = float((d_hip.sqrt() - d_torch.sqrt()).abs().max())
             us_fb = _time_events(fwd_bwd, a.calls, 10)
             g_hip = xg.grad.clone()
-            us_torch_fb = _time_events(torch_fwd_bwd, a.torch_calls, 2)
-            # 0 * inf: autograd through torch.where gives NaN where an unselected branch divides by a rounded-to-zero denominator
-            fin = torch.isfinite(xg.grad)
-            gdiff = float((xg.grad - g_hip)[fin].abs().max() / g_hip.abs().max())
             tests = float(N) * M * F
             rate = lambda us: dict(us=round(us, 1), tests_per_s=float("%.4g" % (tests / us * 1e6)))
-            rec = dict(tool="scan_distance_bench", N=N, M=M, V=V, F=F, split=sd.plan(N, M)[0], max_abs_dist_diff_vs_torch=dmax,
-                       grad_max_rel_diff_vs_torch=gdiff, torch_grad_nonfinite=int((~fin).sum()), fwd=rate(us_fwd), fwd_bwd=rate(us_fb), torch_fwd=rate(us_torch),
-                       torch_fwd_bwd=rate(us_torch_fb), speedup_fwd_vs_torch=round(us_torch / us_fwd, 1),
-                       speedup_fwd_bwd_vs_torch=round(us_torch_fb / us_fb, 1), calls=a.calls, torch_calls=a.torch_calls)
+            rec = dict(tool="scan_distance_bench", N=N, M=M, V=V, F=F, split=sd.plan(N, M)[0], fwd=rate(us_fwd), fwd_bwd=rate(us_fb),
+                       calls=a.calls, torch_calls=a.torch_calls)
+            if a.torch_calls > 0:
+                with torch.no_grad():
+                    us_torch = _time_events(lambda: torch_scan(x, ft, p, a.chunk), a.torch_calls, 2)
+                    d_hip, d_torch = sd.forward(x, p)[0], torch_scan(x, ft, p, a.chunk)
+                    dmax = float((d_hip.sqrt() - d_torch.sqrt()).abs().max())
+                us_torch_fb = _time_events(torch_fwd_bwd, a.torch_calls, 2)
+                # 0 * inf: autograd through torch.where gives NaN where an unselected branch divides by a rounded-to-zero denominator
+                fin = torch.isfinite(xg.grad)
+                gdiff = float((xg.grad - g_hip)[fin].abs().max() / g_hip.abs().max())
+                rec.update(max_abs_dist_diff_vs_torch=dmax, grad_max_rel_diff_vs_torch=gdiff,
+                           torch_grad_nonfinite=int((~fin).sum()), torch_fwd=rate(us_torch), torch_fwd_bwd=rate(us_torch_fb),
+                           speedup_fwd_vs_torch=round(us_torch / us_fwd, 1), speedup_fwd_bwd_vs_torch=round(us_torch_fb / us_fb, 1))
+            if a.cos_min is not None:
+                with torch.no_grad():
+                    us_plain, us_compat = _time_alternating(
+                        [lambda: sd.forward(x, p), lambda: sd.forward(x, p, normals=nrm, cos_min=a.cos_min)], a.calls, 10)
+                    kept = int((sd.forward(x, p, normals=nrm, cos_min=a.cos_min)[1] >= 0).sum())
+                rec.update(cos_min=a.cos_min, fwd_plain_alt=rate(us_plain), fwd_compat=rate(us_compat),
+                           compat_over_plain=round(us_compat / us_plain, 3), points_with_a_face=kept)
             print(json.dumps(rec), flush=True)
             lines.append(rec)
     if a.fit:
